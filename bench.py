@@ -27,6 +27,12 @@ Workloads (--workload):
   config4-slab (32, 16, 1024, 1024) what ONE rank of config4 holds at N = 8: the single-GPU line of the ADMM path
   admm-small (16, 4, 256, 256)    quick functional ADMM run
 
+A plain run does what its headline figure needs and no more: set-up, warm-up, the K timed steps, the JSON line (metric, value, unit,
+ms_per_step, ...; per-kernel times and the roofline from the HIP events of those steps).  --full adds what takes work or runs of its
+own: the CPU baselines (NumPy and C / OpenMP oracle), the live rocprofv3 PMC passes (--pmc auto), the GPU's clocks / power around the
+timed region, and at N > 1 the per-phase pass.  --dump-outputs DIR writes what the timed path computed in its last step (see
+dump_outputs); the inputs are a pure function of the arguments, so two builds can be compared output for output.
+
 --solver cp | admm: default = the solver the workload names (config4* / admm-small: admm, everything else: cp).  A "step" of the ADMM
 bench is ONE outer iteration of pytv.solvers.ADMM as it comes by default (one-sweep dual side tv_admm_sweep + tv_admm_fixup,
 Chebyshev x-solve with --n-cg steps, keep_z=True); metric admm_outer_iters_per_sec.
@@ -61,6 +67,44 @@ WORKLOADS = {
 }
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable
 METRIC = {"cp": "chambolle_pock_iters_per_sec", "admm": "admm_outer_iters_per_sec"}
+DUMP_MAX_VOXELS = 1 << 22       # --dump-outputs: larger volumes are sampled at this many seeded positions (16 MiB of fp32)
+DUMP_SEED = 20240917
+
+
+def sample_iterate(x_local, shape, z0, device, backend):
+    """The final iterate as --dump-outputs writes it, gathered on every rank (collective: all ranks call it): the whole (Nz, M, Ny, Nx)
+    volume when it has at most DUMP_MAX_VOXELS voxels, else the voxels at the sorted, distinct flat indices that
+    np.random.default_rng(DUMP_SEED) draws (DUMP_MAX_VOXELS draws) -- the same positions for any number of ranks.  x_local: this rank's
+    (nz, M, Ny, Nx) view of the solver's iterate (may be strided)."""
+    import torch
+    import torch.distributed as dist
+    Nz, M, Ny, Nx = shape
+    V = Nz * M * Ny * Nx
+    if V <= DUMP_MAX_VOXELS:
+        idx = np.arange(V, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, V, DUMP_MAX_VOXELS, dtype=np.int64))
+    plane = M * Ny * Nx
+    nz = x_local.shape[0]
+    lo, hi = np.searchsorted(idx, [z0 * plane, (z0 + nz) * plane])
+    vals = torch.zeros(len(idx), dtype=torch.float32, device=device)
+    if hi > lo:
+        li = torch.from_numpy(idx[lo:hi] - z0 * plane).to(device)
+        vals[lo:hi] = x_local[li // plane, (li // (Ny * Nx)) % M, (li // Nx) % Ny, li % Nx].float()
+    if dist.is_initialized():
+        red = vals if backend == "nccl" else vals.cpu()
+        dist.all_reduce(red, op=dist.ReduceOp.SUM)          # every position is owned by exactly one rank, the others add 0
+        vals = red
+    out = vals.cpu().numpy()
+    return out.reshape(shape) if V <= DUMP_MAX_VOXELS else out
+
+
+def dump_outputs(dirname, x_sample, loss):
+    """--dump-outputs DIR: x.npy (float32, the final iterate or its sample, see sample_iterate) and loss.npy (float64, the loss of every
+    warm-up and timed step, the last one being the last timed step's)."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "x.npy"), np.ascontiguousarray(x_sample, dtype=np.float32))
+    np.save(os.path.join(dirname, "loss.npy"), np.ascontiguousarray(loss, dtype=np.float64))
 
 
 def synth_slab(shape, z0, nz, device, seed=1234):
@@ -352,7 +396,7 @@ def run_admm(args, wl, shape, slab, device, rank, world, local_rank, backend, co
     for k in range(W):
         ad.step(hist[k])
     ad.timing = []
-    state_before = gpu_state(local_rank) if rank == 0 else None
+    state_before = gpu_state(local_rank) if rank == 0 and args.full else None
     wd.arm("timed region", 120 + 10 * K)
     _test_stall(rank, "timed")
     barrier()
@@ -362,7 +406,8 @@ def run_admm(args, wl, shape, slab, device, rank, world, local_rank, backend, co
     barrier()
     elapsed = time.perf_counter() - t0
     wd.arm("closing collectives", 600)
-    state_after = gpu_state(local_rank) if rank == 0 else None
+    state_after = gpu_state(local_rank) if rank == 0 and args.full else None
+    x_sample = sample_iterate(ad.result(), shape, slab.z0, device, backend) if args.dump_outputs else None
     marks = ad.timing[:K]
     ad.timing = None
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
@@ -375,6 +420,8 @@ def run_admm(args, wl, shape, slab, device, rank, world, local_rank, backend, co
     elapsed = float(tmax.item())
     h = hist_r.cpu().numpy()
     loss = 0.5 * h[:, 1] + 25.0 * h[:, 0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_sample, loss)
     V = float(np.prod(shape))
     V_local = float(slab.nz * shape[1] * shape[2] * shape[3])
     it_s = K / elapsed
@@ -409,8 +456,9 @@ def run_admm(args, wl, shape, slab, device, rank, world, local_rank, backend, co
         "placement_tuning": getattr(ad, "placement", None),
         "rccl_ranks": rccl_ranks, "comm": comm_name,
         "halo": {"backend": (dist.get_backend() if dist.is_initialized() else None), "bytes_per_plane": 4 * shape[1] * shape[2] * shape[3]},
-        "gpu_state": {"before": state_before, "after": state_after, "source": "sysfs (pp_dpm_*, hwmon) read by rank 0 outside the timed region"},
     }
+    if args.full:
+        out["gpu_state"] = {"before": state_before, "after": state_after, "source": "sysfs (pp_dpm_*, hwmon) read by rank 0 outside the timed region"}
     if fused_path:
         out["series_ms"] = {"xsolve": series_summary(s_x), "sweep": series_summary(s_sw), "fixup": series_summary(s_fx),
                             "note": "HIP events on the launch stream at the phase boundaries of every outer iteration"}
@@ -442,7 +490,7 @@ def run_admm(args, wl, shape, slab, device, rank, world, local_rank, backend, co
         out["roofline_fixup"] = {"kernel": "halo exchange of t' + tv_admm_fixup", "ms_per_launch": 1e3 * t_fx, "traffic": traffic.get("fixup")}
     if dist.is_initialized():
         dist.barrier()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if not want_live:
             del ad, x0
         torch.cuda.empty_cache()
@@ -582,14 +630,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="northstar", choices=sorted(WORKLOADS))
     ap.add_argument("--scheme", default="hybrid", choices=["upwind", "downwind", "central", "hybrid"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baselines, live PMC traffic (--pmc auto), GPU clocks / power "
+                         "around the timed region, the per-phase pass at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the final iterate (x.npy, float32; a seeded sample of large volumes) and the loss "
+                         "history (loss.npy, float64) to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--two-kernel", action="store_true", help="force the dual + primal kernel pair instead of the one-sweep kernel")
     ap.add_argument("--comm", default="torch", choices=["torch", "cabi"],
                     help="halo exchange through torch.distributed (RCCL process group, default) or through the C-ABI's own RCCL "
                          "context (tv_ctx_create / tv_halo_exchange; torch.distributed only hands out the unique id)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                    help="auto (1 GPU only): measure roofline.traffic live with two rocprofv3 --pmc child passes after the timed run; "
+                    help="auto (with --full, 1 GPU only): measure roofline.traffic live with two rocprofv3 --pmc child passes after the timed run; "
                          "off: copy the committed numbers of profiles/traffic.json and label them STATIC")
     ap.add_argument("--prewarm-gb", type=float, default=float(os.environ.get("TV_BENCH_PREWARM_GB", "0")),
                     help="touch and release this many GB of device memory before the volume is allocated (placement experiment)")
@@ -627,7 +681,9 @@ def main():
 
     live, live_note = None, "--pmc off"
     want_live = False
-    if args.pmc == "auto":
+    if not args.full:
+        live_note = "live PMC passes run with --full only"
+    elif args.pmc == "auto":
         want_live = (args.gpus == 1 and "RANK" not in os.environ and int(os.environ.get("WORLD_SIZE", "1")) == 1
                      and os.environ.get("TV_BENCH_PMC", "1") != "0")
         if not want_live:
@@ -722,11 +778,11 @@ def main():
     cp.run_steps(hist[:W])
     # per-kernel HIP events on the launch stream (torch's current stream == the stream the C-ABI enqueues on)
     cp.timing = []
-    want_phases = args.phases or world > 1
+    want_phases = args.phases or (world > 1 and args.full)
 
     # (sampled BEFORE the barrier: a sysfs / rocm-smi read on rank 0 between the barrier and t0 would be time the other ranks spend
     # waiting in their first halo exchange -- round-4 advice)
-    state_before = gpu_state(local_rank) if rank == 0 else None
+    state_before = gpu_state(local_rank) if rank == 0 and args.full else None
     wd.arm("timed region", 120 + 10 * K)
     _test_stall(rank, "timed")
     barrier()
@@ -735,7 +791,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     wd.arm("per-phase pass and closing collectives", 600)
-    state_after = gpu_state(local_rank) if rank == 0 else None
+    state_after = gpu_state(local_rank) if rank == 0 and args.full else None
+    # the iterate of the last timed step, before the per-phase pass below iterates on
+    x_sample = sample_iterate(cp.x, shape, slab.z0, device, backend) if args.dump_outputs else None
     ev = cp.timing[:K]
     cp.timing = None
     phases = None
@@ -776,6 +834,8 @@ def main():
     elapsed = float(tmax.item())
     h = hist_r.cpu().numpy()
     loss = cp.loss_from_slots(h, 25.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_sample, loss)
 
     V = float(np.prod(shape))
     V_local = float(slab.nz * shape[1] * shape[2] * shape[3])
@@ -822,7 +882,8 @@ def main():
     out["series_ms"] = {"kernel1": series_summary(s_k1), "kernel2": series_summary(s_k2),
                         "step": series_summary([a.elapsed_time(b) for (a, _, _), (b, _, _) in zip(ev[:-1], ev[1:])]) if len(ev) > 1 else None,
                         "note": "kernel1 = sweep (or dual), kernel2 = fix-up (or primal), step = start of iteration k to start of k+1"}
-    out["gpu_state"] = {"before": state_before, "after": state_after, "source": "sysfs (pp_dpm_*, hwmon) read by rank 0 outside the timed region"}
+    if args.full:
+        out["gpu_state"] = {"before": state_before, "after": state_after, "source": "sysfs (pp_dpm_*, hwmon) read by rank 0 outside the timed region"}
     cp_fused = bool(cp.fused)
     wd.arm("post-run: live PMC passes, CPU baseline on rank 0, final barrier", 1800)
     if want_live:
@@ -869,7 +930,7 @@ def main():
                                   "note": "algorithmic bytes (Nd+5)*4 per voxel: reads q,x,x0,p; writes x,p (fidelity dual fused in)" + sharded}
     if dist.is_initialized():
         dist.barrier()          # the other ranks wait at the final barrier while rank 0 times the host baseline
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if not want_live:
             del cp, x0
         torch.cuda.empty_cache()

@@ -170,8 +170,8 @@ def gen_trajectories():
 
 def gen_trajectory_512():
     """BASELINE configs[0] at its SIZE (512 x 512, hybrid sub-gradient loop, 300 iterations, README.md:107-124) on a
-    synthetic phantom -- the cameraman image itself is the reference's data and stays in /root/reference
-    (tests/test_oracle_vs_reference.py pins the oracle on it in the authoring container).  Only the phantom (it
+    synthetic phantom -- the cameraman image itself is stored on its own (gen_cameraman: cameraman.npz, which
+    tests/test_oracle_vs_reference.py pins the oracle on).  Only the phantom (it
     compresses), the seed and the outputs are stored: the noise is np.random.RandomState(0).rand, which NumPy keeps
     bit-stable across versions."""
     noise_level, nb_it, regularization, step_size = 100, 300, 25, 5e-3
@@ -192,10 +192,84 @@ def gen_trajectory_512():
     print("wrote trajectory_512.npz")
 
 
+# the degenerate geometries of the oracle sweep (tests/test_oracle_vs_reference.py): tiny frames, central has no interior row /
+# column at N = 2.  The inputs are drawn from np.random.default_rng(11) in exactly this order (mask, x, y), so that the test
+# regenerates them; only the reference's outputs are stored.  x is a binary image (0 / 1, with a flat 0.25 patch in the first
+# 2 x 2 corner of every frame) and y takes the values -1, 0, 1: differences of every sign, ties and zero gradients everywhere, and
+# outputs that compress (the sub-gradient still divides by irrational norms).
+SWEEP_GEOMS = [(1, 1, 9, 9), (4, 1, 8, 8), (3, 1, 7, 7), (5, 1, 6, 6), (1, 3, 7, 7), (4, 2, 6, 6), (3, 3, 6, 6), (5, 4, 7, 7), (6, 8, 5, 5),
+               (3, 1, 2, 2), (4, 3, 2, 2), (1, 1, 3, 3), (3, 3, 4, 4)]
+SWEEP_PARAMS = ((1.0, 0.0), (0.0, 0.0), (2.5, 1.0), (1.0, 2 ** -5), (0.0, 0.7))
+
+
+def sweep_cases():
+    """(scheme, shape, reg_z_over_reg, reg_time, use_mask) in the order of the sweep"""
+    for scheme in SCHEMES:
+        for shape in SWEEP_GEOMS:
+            for lz, mu in SWEEP_PARAMS:
+                for use_mask in (False, True):
+                    if use_mask and not (mu > 0 and shape[1] > 1):
+                        continue
+                    yield scheme, shape, lz, mu, use_mask
+
+
+def gen_reference_sweep():
+    """D, D^T, TV, G and the infinite-norm pattern of the reference's CPU twin over the sweep (float64), every case's arrays
+    flattened and concatenated in the sweep's order; an .npz, xz-compressed."""
+    import io
+    import lzma
+    rng = np.random.default_rng(11)
+    D, DT, G, tv, ninf, dshape = [], [], [], [], [], []
+    for scheme, shape, lz, mu, use_mask in sweep_cases():
+        mask = (rng.random((1, 1) + shape[2:]) > 0.4) if use_mask else False
+        kw = dict(reg_z_over_reg=lz, reg_time=mu, mask_static=mask, factor_reg_static=3.0 if use_mask else 0)
+        x = rng.integers(0, 2, shape).astype(np.float64)
+        x[..., :2, :2] = 0.25
+        Dr = getattr(ops, "D_" + scheme)(x.copy(), **kw)
+        y = rng.integers(-1, 2, Dr.shape).astype(np.float64)
+        tr, Gr, nr = getattr(tvc, "tv_" + scheme)(x.copy(), return_grad_norms=True, **kw)
+        D.append(Dr.ravel())
+        DT.append(getattr(ops, "D_T_" + scheme)(y.copy(), **kw).ravel())
+        G.append(Gr.ravel())
+        tv.append(tr)
+        ninf.append(np.isinf(nr).ravel())
+        dshape.append(Dr.shape)
+    buf = io.BytesIO()
+    np.savez(buf, D=np.concatenate(D), DT=np.concatenate(DT), G=np.concatenate(G), tv=np.array(tv, dtype=np.float64),
+             norms_inf=np.packbits(np.concatenate(ninf)), D_shape=np.array(dshape, dtype=np.int32))
+    with open(os.path.join(OUT, "reference_sweep.npz.xz"), "wb") as f:
+        f.write(lzma.compress(buf.getvalue(), preset=9 | lzma.PRESET_EXTREME))
+    print("wrote reference_sweep.npz.xz (%d cases)" % len(tv))
+
+
+def gen_cameraman():
+    """BASELINE configs[0] on its real image: the reference's cameraman (256 x 256, values 7 .. 253, stored as uint8) and the
+    reference's own README sub-gradient loop on it (hybrid, 300 iterations, np.random.seed(0) noise): the loss of every iteration."""
+    cam = np.asarray(pytv.utils.cameraman())
+    assert cam.shape == (256, 256) and cam.min() == 7 and cam.max() == 253 and np.array_equal(cam, cam.astype(np.uint8))
+    np.random.seed(0)
+    truth = np.reshape(cam, (1, 1, 256, 256))
+    noisy = truth + 100 * np.random.rand(*truth.shape)
+    est = np.copy(noisy)
+    loss = np.zeros(300)
+    for it in range(300):
+        tvv, G = tvc.tv_hybrid(est)
+        est += -5e-3 * ((est - noisy) + 25 * G)
+        loss[it] = 0.5 * np.sum(np.square(est - noisy)) + 25 * tvv
+    np.savez_compressed(os.path.join(OUT, "cameraman.npz"), image=cam.astype(np.uint8), gd_loss_hybrid_256=loss)
+    print("wrote cameraman.npz")
+
+
 if __name__ == "__main__":
+    if "--only-sweep" in sys.argv:            # the two fixtures of tests/test_oracle_vs_reference.py alone
+        gen_reference_sweep()
+        gen_cameraman()
+        sys.exit(0)
     if "--only-512" not in sys.argv:
         gen_ops()
         gen_known_answers()
         gen_trajectories()
     gen_trajectory_512()
+    gen_reference_sweep()
+    gen_cameraman()
     sys.exit(0)

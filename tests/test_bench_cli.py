@@ -141,3 +141,24 @@ def test_watchdog_ends_a_stuck_process_with_an_error_line():
     code2 = code.replace("time.sleep(30)", "w.disarm(); time.sleep(3)")
     p = subprocess.run([sys.executable, "-c", code2], capture_output=True, text=True, timeout=60)
     assert p.returncode == 0 and "NOT REACHED" in p.stdout
+
+
+def test_dump_sample_is_fixed_and_the_same_for_any_slab_split(monkeypatch, tmp_path):
+    """--dump-outputs (no GPU needed: CPU tensors): small volumes are written whole; larger ones at seeded flat indices that do not depend
+    on how the volume is split into z-slabs or on the layout of the solver's storage (strided views of padded rows)."""
+    import torch
+    x = torch.arange(4 * 2 * 3 * 5, dtype=torch.float32).reshape(4, 2, 3, 5)
+    assert np.array_equal(bench.sample_iterate(x, (4, 2, 3, 5), 0, "cpu", None), x.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_VOXELS", 50)
+    shape = (6, 2, 4, 5)
+    x = torch.rand(shape, generator=torch.Generator().manual_seed(3))
+    padded = torch.zeros((6, 2, 4, 8))
+    padded[..., :5] = x
+    full = bench.sample_iterate(padded[..., :5], shape, 0, "cpu", None)
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, x.numel(), 50))
+    assert full.shape == idx.shape and np.array_equal(full, x.numpy().reshape(-1)[idx])
+    parts = [bench.sample_iterate(x[a:b], shape, a, "cpu", None) for a, b in ((0, 1), (1, 4), (4, 6))]
+    assert np.array_equal(sum(parts), full)
+    assert np.array_equal(bench.sample_iterate(x, shape, 0, "cpu", None), full)
+    bench.dump_outputs(str(tmp_path / "out"), full, np.arange(3.0))
+    assert np.load(tmp_path / "out" / "x.npy").dtype == np.float32 and np.load(tmp_path / "out" / "loss.npy").dtype == np.float64

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -117,7 +118,7 @@ def test_bench_sharded_over_ranks_gives_the_single_rank_loss(ranks):
     env2 = dict(env, TV_BENCH_BACKEND="gloo", TV_BENCH_SHARE_GPU="1", TV_ZCHUNK="1")      # short chunks: interior-first schedule
     many = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
                         "--master-addr", "127.0.0.1", "--master-port", str(29640 + ranks), os.path.join(ROOT, "bench.py"),
-                        "--gpus", str(ranks)] + common, env2)
+                        "--gpus", str(ranks), "--full"] + common, env2)
     assert many["n_gpus"] == ranks and many["steps"] == 6 and many["scaling"] == "strong"
     assert "cpu_baseline" in many and many["cpu_baseline"]["cores"] == 1
     assert "roofline" in many and many["rccl_ranks"] == 0            # the test transport is not RCCL
@@ -132,6 +133,31 @@ def test_bench_sharded_over_ranks_gives_the_single_rank_loss(ranks):
     assert all(ph["max_over_ranks"][k] >= ph["mean_over_ranks"][k] - 1e-9 for k in want)
     assert sum(ph["mean_over_ranks"].values()) <= 1.5 * many["ms_per_step"]
     assert "phases" not in one
+
+
+def test_bench_dump_outputs_are_the_same_for_one_and_two_ranks(tmp_path):
+    """--dump-outputs: a plain one-GPU line (no CPU baseline, no gpu_state, no phases) that writes the final iterate (the whole
+    16 x 4 x 256 x 256 volume) and the loss of every step; the same job over two TEST ranks (gloo, both on cuda:0) writes the same
+    arrays, and a second one-rank run repeats the first."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TV_BENCH_BACKEND", "TV_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    common = ["--workload", "small", "--steps", "5", "--warmup", "2"]
+    one = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / "a")] + common, env)
+    assert one["steps"] == 5 and one["ms_per_step"] > 0 and one["dtype"] == "f32"
+    assert not {"cpu_baseline", "cpu_baseline_openmp", "gpu_state", "phases"} & set(one)
+    again = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / "b")] + common, env)
+    env2 = dict(env, TV_BENCH_BACKEND="gloo", TV_BENCH_SHARE_GPU="1", TV_ZCHUNK="1")
+    two = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                       "--master-port", "29648", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path / "c")] + common,
+                      env2)
+    assert two["n_gpus"] == 2 and again["n_gpus"] == 1
+    xa, la = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "loss.npy")
+    assert xa.dtype == np.float32 and xa.shape == (16, 4, 256, 256) and la.dtype == np.float64 and la.shape == (7,)
+    np.testing.assert_allclose(la[[2, -1]], one["loss_first_last"], rtol=1e-12)
+    for d in ("b", "c"):
+        np.testing.assert_allclose(np.load(tmp_path / d / "x.npy"), xa, rtol=1e-5, atol=1e-3)
+        np.testing.assert_allclose(np.load(tmp_path / d / "loss.npy"), la, rtol=1e-6)
 
 
 def test_n8_rehearsal_eight_ranks_on_one_gpu():
@@ -149,7 +175,7 @@ def test_n8_rehearsal_eight_ranks_on_one_gpu():
     one = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, env1)
     env8 = dict(env, TV_BENCH_BACKEND="gloo", TV_BENCH_SHARE_GPU="1", TV_ZCHUNK="2")      # 2-plane chunks: 4 chunks per 8-plane slab
     many = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                        "--master-port", "29658", os.path.join(ROOT, "bench.py"), "--gpus", "8"] + common, env8)
+                        "--master-port", "29658", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full"] + common, env8)
     assert many["n_gpus"] == 8 and many["steps"] == 4 and many["scaling"] == "strong" and many["rccl_ranks"] == 0
     assert many["config"]["shape"] == [64, 8, 1024, 1024] and "z-slab x8" in many["config"]["parallelism"]
     a, b = one["loss_first_last"], many["loss_first_last"]
@@ -166,7 +192,7 @@ def test_bench_admm_line_on_one_gpu():
     admm_outer_iters_per_sec, a roofline block on the one-sweep dual-side kernel with its words per voxel, the x-solve beside it."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "admm-small", "--steps", "6", "--warmup", "2",
-                       "--pmc", "off", "--scheme", "upwind"], env)
+                       "--pmc", "off", "--scheme", "upwind", "--full"], env)
     assert out["metric"] == "admm_outer_iters_per_sec" and out["unit"] == "it/s" and out["value"] > 0 and out["n_gpus"] == 1
     assert out["config"]["workload"].startswith("admm-small 16x4x256x256") and out["config"]["x_solver"] == "chebyshev"
     nd, n_cg = out["config"]["nd"], out["config"]["n_cg"]
@@ -242,7 +268,7 @@ def test_bench_measures_its_hbm_traffic_live():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     r = out["roofline"]
@@ -265,7 +291,7 @@ def test_gpus_2_from_a_plain_shell_launches_itself_and_matches_one_rank():
     TEST transport (gloo, both ranks on cuda:0) the 2-rank loss equals the 1-rank loss."""
     common = ["--workload", "rehearsal", "--nz", "8", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--pmc", "off"]
     one = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, _shell_env(TV_ZCHUNK="2"))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + common,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + common,
                        env=_shell_env(TV_BENCH_BACKEND="gloo", TV_BENCH_SHARE_GPU="1", TV_ZCHUNK="2"), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
     assert "self-launch (torch imported: False)" in p.stderr

@@ -4,16 +4,16 @@
 # operator rooflines, the descent loop, the reference's own small shapes, rocprofv3 kernel traces of the same commands and the PMC passes.
 TAG=${1:-r6}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; cd $R; O=$R/gpurun_out; mkdir -p $O
-python3 bench.py > $O/${TAG}_bench_default_first_command.json 2> $O/${TAG}_bench_err.txt
+python3 bench.py --full > $O/${TAG}_bench_default_first_command.json 2> $O/${TAG}_bench_err.txt
 for s in upwind downwind central hybrid; do
-  python3 bench.py --solver admm --workload config4-slab --scheme $s --steps 10 --warmup 3 > $O/${TAG}_bench_admm_config4slab_$s.json 2>> $O/${TAG}_bench_err.txt
+  python3 bench.py --full --solver admm --workload config4-slab --scheme $s --steps 10 --warmup 3 > $O/${TAG}_bench_admm_config4slab_$s.json 2>> $O/${TAG}_bench_err.txt
 done
 for s in upwind downwind central; do
-  python3 bench.py --scheme $s --steps 12 --warmup 4 --no-cpu-baseline > $O/${TAG}_bench_northstar_$s.json 2>> $O/${TAG}_bench_err.txt
+  python3 bench.py --full --scheme $s --steps 12 --warmup 4 --no-cpu-baseline > $O/${TAG}_bench_northstar_$s.json 2>> $O/${TAG}_bench_err.txt
 done
-python3 bench.py --workload config1 --steps 50 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_config1.json 2>> $O/${TAG}_bench_err.txt
-python3 bench.py --workload config2 --steps 30 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_config2.json 2>> $O/${TAG}_bench_err.txt
-python3 bench.py --workload config3 --allow-single --steps 6 --warmup 2 --no-cpu-baseline --pmc off > $O/${TAG}_bench_config3_single_gpu.json 2>> $O/${TAG}_bench_err.txt
+python3 bench.py --full --workload config1 --steps 50 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_config1.json 2>> $O/${TAG}_bench_err.txt
+python3 bench.py --full --workload config2 --steps 30 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_config2.json 2>> $O/${TAG}_bench_err.txt
+python3 bench.py --full --workload config3 --allow-single --steps 6 --warmup 2 --no-cpu-baseline --pmc off > $O/${TAG}_bench_config3_single_gpu.json 2>> $O/${TAG}_bench_err.txt
 python3 tools/op_bench.py 64x8x1024x1024 hybrid upwind downwind central > $O/${TAG}_op_rooflines.txt 2>&1
 SG_TUNE=0 python3 tools/sg_bench.py 256x8x1024x1024 hybrid upwind downwind central > $O/${TAG}_sg_loop_northstar.txt 2>&1
 python3 tools/small_volume_bench.py --schemes hybrid,upwind,downwind,central 20x4x100x100 1x1x512x512 1x1x256x256 20x1x100x100 2>&1 | grep -v amdgpu.ids > $O/${TAG}_small_volume_bench.txt

@@ -23,6 +23,11 @@ UNITS = [u[:-len(".hip")] for u in _product_build.UNITS]
 SAN = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-g", "-O1"]
 
 
+def _preload(rt):
+    """the sanitizer runtime first, whatever the environment already preloads after it"""
+    return " ".join([rt] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
+
+
 def run(cmd, **kw):
     print("[sanitize] " + " ".join(cmd), flush=True)
     return subprocess.run(cmd, **kw)
@@ -33,7 +38,7 @@ def oracle_leg(tmp):
     run(["gcc"] + SAN + ["-fopenmp", "-shared", "-fPIC", "-std=c11", os.path.join(ROOT, "oracle", "tv_oracle_c.c"), "-o", out, "-lm"],
         check=True)
     rt = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1",
+    env = dict(os.environ, LD_PRELOAD=_preload(rt), ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1",
                TV_ORACLE_C_LIB=out, OMP_NUM_THREADS="4")
     p = run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_c.py")], env=env, cwd=ROOT)
     return p.returncode
@@ -41,7 +46,7 @@ def oracle_leg(tmp):
 
 def host_leg(tmp):
     hipcc = "/opt/rocm/bin/hipcc"
-    flags = ["--cuda-host-only"] + SAN + ["-std=c++20", "-fPIC", "-Wno-unused-value"]
+    flags = ["--cuda-host-only", "-fno-gpu-sanitize"] + SAN + ["-std=c++20", "-fPIC", "-Wno-unused-value"]
 
     def comp(u):
         obj = os.path.join(tmp, u + ".o")
@@ -63,9 +68,9 @@ def host_leg(tmp):
             f.write('const char %s[64] __attribute__((aligned(4096))) = "__CLANG_OFFLOAD_BUNDLE__";\n' % s)
     subprocess.check_call(["gcc", "-c", "-fPIC", stub, "-o", stub[:-2] + ".o"])
     out = os.path.join(tmp, "libpytv4d_host_asan.so")
-    run([hipcc, "-fsanitize=address,undefined", "-shared", "-fPIC", "-o", out] + objs + [stub[:-2] + ".o"], check=True)
+    run([hipcc, "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-shared", "-fPIC", "-o", out] + objs + [stub[:-2] + ".o"], check=True)
     rt = subprocess.check_output(["/opt/rocm/lib/llvm/bin/clang", "--print-file-name=libclang_rt.asan-x86_64.so"], text=True).strip()
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1",
+    env = dict(os.environ, LD_PRELOAD=_preload(rt), ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1",
                PYTV4D_LIB=out)
     p = run([sys.executable, os.path.join(ROOT, "tools", "abi_validation.py")], env=env, cwd=ROOT)
     return p.returncode

@@ -342,7 +342,9 @@ int tv_subgrad_step(const tv_geom* g, void* x, const void* x0, const void* G, do
  *                              (the blocks' phase counters continue from call to call: no reset per launch).  One `ws` per stream.
  *                              Safety net: should the blocks of a launch not all become resident (they wait for each other), the launch
  *                              abandons itself after ~2 s of polling instead of hanging: every hist entry of the call is NaN, the state
- *                              arrays are undefined and `ws` must be zero-filled again.
+ *                              arrays are undefined and `ws` must be zero-filled again.  The verdict is the ABORT word, 32-bit word
+ *                              8192 * 32 + 1 of `ws` (non-zero after an abandoned call), not the history: a diverging iteration or a
+ *                              NaN in the input gives non-finite history entries from a launch that completed.
  *   tv_small_cp              : n_iter iterations of  p <- (p + sigma_A (x - x0)) / (1 + sigma_A);  q <- proj(q + sigma_D D x);
  *                              x <- x - tau p - tau D^T q  exactly as tv_cp_dual + tv_cp_primal compute them, x / p / q updated in
  *                              place.  hist (device fp64): hist[k * hist_stride] = |D x_k|_{2,1} (the iterate the dual update of

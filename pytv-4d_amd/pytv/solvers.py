@@ -166,14 +166,20 @@ class _SlabProblem:
             self._small_ws_buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
         return self._small_ws_buf
 
-    def _small_check(self, loss):
-        """the persistent kernels abandon a launch whose blocks cannot all run at once instead of hanging (csrc/tv_small.hip, small_sync): NaN history"""
-        import numpy as _np
-        if not _np.all(_np.isfinite(loss)):
+    # 32-bit word of the workspace that a launch raises when it abandons itself (csrc/tv_small.hip: small_abort_word, kMaxSmallBlocks * kFlagStride + 1)
+    SMALL_ABORT_WORD = 8192 * 32 + 1
+
+    def _small_check(self):
+        """the persistent kernels abandon a launch whose blocks cannot all run at once instead of hanging (csrc/tv_small.hip, small_sync): they
+        raise the workspace's abort word.  That word is the verdict, not the loss: a diverging iteration or a NaN in the input gives a non-finite
+        loss on every path and is returned as it is.  An abandoned workspace is dropped (the next launch gets a zero-filled one)."""
+        ws = getattr(self, "_small_ws_buf", None)
+        if ws is None:
+            return
+        if int(ws.view(torch.int32)[self.SMALL_ABORT_WORD].item()) != 0:        # one 4-byte device-to-host copy (waits for the launches)
             self._small_ws_buf = None
-            raise RuntimeError("the persistent small-volume kernel returned a non-finite loss: either the iteration diverged or the launch was abandoned "
-                               "(its blocks were not resident together); construct the solver with persistent=False or lower TV_SMALL_BLOCKS_PER_CU")
-        return loss
+            raise RuntimeError("the persistent small-volume kernel abandoned its launch (its blocks were not resident together); the state is "
+                               "undefined: construct the solver with persistent=False or lower TV_SMALL_BLOCKS_PER_CU")
 
     def geom(self, a, b):
         """Geometry of local planes [a, b) seen as a slab of the global volume."""
@@ -803,7 +809,8 @@ class ChambollePock(_SlabProblem):
         small enough to be launch-bound and not sharded; True / False force it."""
         hist = torch.zeros((n_iter, self.SLOTS), dtype=torch.float64, device=self.device)
         use_graph = (self.x0.numel() <= self.GRAPH_MAX_VOXELS and not self.slab.sharded and self.timing is None and self.phase_timing is None) if graph is None else bool(graph)
-        if self._small_now() and graph is None:
+        small = self._small_now()
+        if small and graph is None:
             use_graph = False                     # the persistent kernel IS the loop: nothing left to capture
         start = 0
         if use_graph and n_iter >= 2 + 2 * self.GRAPH_BLOCK and not self.slab.sharded:
@@ -813,11 +820,12 @@ class ChambollePock(_SlabProblem):
             done = self._run_graphed_from(hist, 2, n_iter)
             start = 2 + max(done, 0)
         self.run_steps(hist[start:n_iter])
+        if small:
+            self._small_check()
         if not record_loss:
             return None
         self.slab.allreduce_sum_(hist)
-        loss = self.loss_from_slots(hist.cpu().numpy(), self.reg)
-        return self._small_check(loss) if self.small else loss
+        return self.loss_from_slots(hist.cpu().numpy(), self.reg)
 
     def run_steps(self, rows):
         """Enqueue ``len(rows)`` iterations, row k of the (n, SLOTS) fp64 device tensor ``rows`` receiving the scalars of iteration k.
@@ -1195,7 +1203,8 @@ class SubgradientDescent(_SlabProblem):
         hist = torch.zeros((n_iter, self.SLOTS), dtype=torch.float64, device=self.device)
         if self.small and graph is None:
             self._run_small(hist)
-            return self._small_check(self.loss_from_slots(hist.cpu().numpy(), self.reg))
+            self._small_check()
+            return self.loss_from_slots(hist.cpu().numpy(), self.reg)
         use_graph = (self.x0.numel() <= self.GRAPH_MAX_VOXELS) if graph is None else bool(graph)
         start = 0
         if use_graph and not self.slab.sharded and n_iter >= 2 + 2 * self.GRAPH_BLOCK:

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_cp(DG g, WT<T> w, Small
 // one round trip), computes, and stores only what neighbours read (x; the dual channels).  Sites are numbered FLAT inside a frame (row-major
 // site-vectors, blockDim.x per block: no lanes wasted on frames narrower than a block), frames and planes as above.  Arithmetic: d_slots + the
 // CpDual / dt_site / CpPrimal expressions in their order.  Not with a per-voxel weight volume (generic kernel).
-constexpr unsigned kOOB = 0x80000000u;          // every array of these kernels is below 2^31 bytes (small_check)
+constexpr unsigned kOOB = 0x80000000u;          // every array of these kernels is below 2^31 bytes (small_fits)
 // Block size of the register-resident kernels: chosen per volume (small_plan_flat) so that every CU gets the SAME number of waves.  With a
 // fixed 256 threads the (20,4,100,100) volume makes 800 blocks on 256 CUs -- 3 or 4 per CU, and the blocks of the CUs that hold 4 run every
 // phase 1.5 x slower and pace all the others through the neighbour waits; one-wave blocks spread evenly but multiply the flags and the
@@ -303,6 +303,32 @@ template <typename T, int V> __device__ __forceinline__ void coh_stv(const CohMe
         typedef int v4i __attribute__((ext_vector_type(4)));
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), m.r, (int)byte_off, 0, CohMem::AUX);
     }
+}
+
+// byte offset of an access: valid ? base + delta : kOOB (out of range: a load gives 0, a store is dropped -- no branch around an access)
+__device__ __forceinline__ unsigned coh_at(bool valid, unsigned base, int delta) { return valid ? base + (unsigned)delta : kOOB; }
+
+// wave-uniform byte deltas (SGPRs) to the next row, frame and plane of an image and to the next plane of the dual array
+struct SmallDeltas { int row, frame, plane, qplane; };
+template <typename T> __device__ __forceinline__ SmallDeltas small_deltas(const DG& g) {
+    constexpr unsigned EB = sizeof(T);
+    return SmallDeltas{g.rp * (int)EB, (int)(g.s_t * EB), (int)(g.s_z * EB), (int)(g.s_dz * EB)};
+}
+
+// n <- the site-vector c of an image-like array at byte offset b and its neighbours (flags: n's; an absent one is out of range and reads 0);
+// head / tail: the elements just before / after c.  NEXT / PREV: the sides the caller reads (load_xn), the others stay 0.
+template <bool NEXT, bool PREV, typename T, int V>
+__device__ __forceinline__ void coh_neighbours(const CohMem& m, unsigned b, const SmallDeltas& bd, bool has_head, bool has_tail, const Vec<T, V>& c,
+                                               XN<T, V>& n, T& head, T& tail) {
+    constexpr int EB = sizeof(T);
+    n.c = c;
+    n.nr = coh_ldv<T, V>(m, coh_at(NEXT && n.h_nr, b, bd.row)); n.pr = coh_ldv<T, V>(m, coh_at(PREV && n.h_pr, b, -bd.row));
+    n.nz = coh_ldv<T, V>(m, coh_at(NEXT && n.h_nz, b, bd.plane)); n.pz = coh_ldv<T, V>(m, coh_at(PREV && n.h_pz, b, -bd.plane));
+    n.nt = coh_ldv<T, V>(m, coh_at(NEXT && n.h_nt, b, bd.frame)); n.pt = coh_ldv<T, V>(m, coh_at(PREV && n.h_pt, b, -bd.frame));
+    tail = coh_ld1<T>(m, coh_at(NEXT && has_tail, b, V * EB));
+    head = coh_ld1<T>(m, coh_at(PREV && has_head, b, -EB));
+    n.nc = NEXT ? shift_left<T, V>(c, tail) : vsplat<T, V>(T(0));
+    n.pc = PREV ? shift_right<T, V>(c, head) : vsplat<T, V>(T(0));
 }
 
 // flat numbering: block J = tile * (m nz) + plane * m + frame (TILE-MAJOR: consecutive J -- one XCD -- hold all frames and planes of a band of
@@ -362,7 +388,6 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
     const long long offx = (long long)zl * g.s_z + inpl, offq = (long long)zl * g.s_dz + inpl;
     const CohMem mx = CohMem::make(a.x, a.x_bytes), mq = CohMem::make(a.q, a.q_bytes);
     const Vec<T, V> zero = vsplat<T, V>(T(0));
-    auto bo = [&](bool valid, long long elem) -> unsigned { return valid ? (unsigned)(elem * EB) : kOOB; };
     // ---- the neighbourhood, once
     XN<T, V> n;
     n.col0 = col0;
@@ -380,7 +405,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
     // valid ? base + delta : kOOB, two VALU instructions at the point of use (the bases pass through an empty asm every iteration so that the
     // sums are not hoisted back into registers).
     const unsigned bx0 = (unsigned)(offx * EB), bq0 = (unsigned)(offq * EB);
-    const int d_row = g.rp * (int)EB, d_frame = (int)(g.s_t * EB), d_plane = (int)(g.s_z * EB), d_qplane = (int)(g.s_dz * EB);
+    const SmallDeltas bd = small_deltas<T>(g);
     // dual channels: byte delta of slot k from channel 0 at my site, < 0 for inactive slots (their loads give 0, their stores are dropped)
     int dq[NS];
 #pragma unroll
@@ -388,7 +413,6 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
     for_each_channel<S>(g, [&](auto slot, int ch) {
         if constexpr (decltype(slot)::value < NS) dq[decltype(slot)::value] = (int)((long long)ch * g.s_z * EB);
     });
-    auto at = [&](bool valid, unsigned base, int delta) -> unsigned { return valid ? base + (unsigned)delta : kOOB; };
     // neighbours the adjoint reads: slot `up` one step back, slot `down` one step ahead along each axis (the same slot unless hybrid)
     constexpr int U_R = 0, U_C = 1, U_Z = (S == HYBRID) ? 4 : 2, U_T = (S == HYBRID) ? 6 : 3;
     constexpr int D_R = (S == HYBRID) ? 2 : 0, D_C = (S == HYBRID) ? 3 : 1, D_Z = (S == HYBRID) ? 5 : 2, D_T = (S == HYBRID) ? 7 : 3;
@@ -399,7 +423,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
     Vec<T, V> p = ok ? vload<T, V>(a.p + offx) : zero;
     Vec<T, V> q[NS];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) q[k] = coh_ldv<T, V>(mq, at(ok && dq[k] >= 0, bq0, dq[k]));
+    for (int k = 0; k < NS; ++k) q[k] = coh_ldv<T, V>(mq, coh_at(ok && dq[k] >= 0, bq0, dq[k]));
     const Vec<T, V> mf = (ok && g.ta) ? mask_factor<T, V>(g, w.sf, y, col0) : vsplat<T, V>(T(1));
     const int gz = zl;          // unsharded: z0 == 0
 
@@ -408,13 +432,8 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
         // ---- dual: q <- proj(q + sigma D x), TV(x) (README.md:149-151): every neighbour of x at once
         unsigned bx = bx0, bq = bq0;
         asm volatile("" : "+v"(bx), "+v"(bq));
-        n.c = x;
-        n.nr = coh_ldv<T, V>(mx, at(NEXT && n.h_nr, bx, d_row)); n.pr = coh_ldv<T, V>(mx, at(PREV && n.h_pr, bx, -d_row));
-        n.nz = coh_ldv<T, V>(mx, at(NEXT && n.h_nz, bx, d_plane)); n.pz = coh_ldv<T, V>(mx, at(PREV && n.h_pz, bx, -d_plane));
-        n.nt = coh_ldv<T, V>(mx, at(NEXT && n.h_nt, bx, d_frame)); n.pt = coh_ldv<T, V>(mx, at(PREV && n.h_pt, bx, -d_frame));
-        const T x_tail = coh_ld1<T>(mx, at(NEXT && has_tail, bx, V * (int)EB)), x_head = coh_ld1<T>(mx, at(PREV && has_head, bx, -(int)EB));
-        n.nc = NEXT ? shift_left<T, V>(x, x_tail) : zero;
-        n.pc = PREV ? shift_right<T, V>(x, x_head) : zero;
+        T x_head, x_tail;
+        coh_neighbours<NEXT, PREV>(mx, bx, bd, has_head, has_tail, x, n, x_head, x_tail);
         double acc = 0.0;
         {
             Vec<T, V> o[8];
@@ -435,7 +454,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 q[k] = q[k] * scale;
-                coh_stv<T, V>(mq, at(ok && dq[k] >= 0, bq, dq[k]), q[k]);
+                coh_stv<T, V>(mq, coh_at(ok && dq[k] >= 0, bq, dq[k]), q[k]);
             }
             if (!ok) acc = 0.0;
         }
@@ -446,10 +465,10 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
         TV_SMALL_MARK(2);
         // ---- primal: p <- (p + sigma_A (x - x0)) / (1 + sigma_A); x <- x - tau p - tau D^T q (README.md:148,154): every neighbour of q at once
         asm volatile("" : "+v"(bx), "+v"(bq));
-        const Vec<T, V> lo_r = coh_ldv<T, V>(mq, at(LO && n.h_pr, bq, dq[U_R] - d_row)), hi_r = coh_ldv<T, V>(mq, at(HI && n.h_nr, bq, dq[D_R] + d_row));
-        const Vec<T, V> lo_z = coh_ldv<T, V>(mq, at(LO && n.h_pz, bq, dq[U_Z] - d_qplane)), hi_z = coh_ldv<T, V>(mq, at(HI && n.h_nz, bq, dq[D_Z] + d_qplane));
-        const Vec<T, V> lo_t = coh_ldv<T, V>(mq, at(LO && n.h_pt, bq, dq[U_T] - d_frame)), hi_t = coh_ldv<T, V>(mq, at(HI && n.h_nt, bq, dq[D_T] + d_frame));
-        const T q_head = coh_ld1<T>(mq, at(LO && has_head, bq, dq[U_C] - (int)EB)), q_tail = coh_ld1<T>(mq, at(HI && has_tail, bq, dq[D_C] + V * (int)EB));
+        const Vec<T, V> lo_r = coh_ldv<T, V>(mq, coh_at(LO && n.h_pr, bq, dq[U_R] - bd.row)), hi_r = coh_ldv<T, V>(mq, coh_at(HI && n.h_nr, bq, dq[D_R] + bd.row));
+        const Vec<T, V> lo_z = coh_ldv<T, V>(mq, coh_at(LO && n.h_pz, bq, dq[U_Z] - bd.qplane)), hi_z = coh_ldv<T, V>(mq, coh_at(HI && n.h_nz, bq, dq[D_Z] + bd.qplane));
+        const Vec<T, V> lo_t = coh_ldv<T, V>(mq, coh_at(LO && n.h_pt, bq, dq[U_T] - bd.frame)), hi_t = coh_ldv<T, V>(mq, coh_at(HI && n.h_nt, bq, dq[D_T] + bd.frame));
+        const T q_head = coh_ld1<T>(mq, coh_at(LO && has_head, bq, dq[U_C] - (int)EB)), q_tail = coh_ld1<T>(mq, coh_at(HI && has_tail, bq, dq[D_C] + V * (int)EB));
         Vec<T, V> r = zero, rt = zero;
         auto rows = [&](auto mode, const Vec<T, V>& ce_q) {
             constexpr int M = decltype(mode)::value;
@@ -514,7 +533,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_reg(DG g, WT<T> w, 
             acc += 0.5 * e * e;
         }
         if (!ok) acc = 0.0;
-        coh_stv<T, V>(mx, at(ok, bx, 0), x);
+        coh_stv<T, V>(mx, coh_at(ok, bx, 0), x);
         acc = block_sum(acc, sm);
         if (threadIdx.x == 0) a.partials[((long long)it * 2 + 1) * sp.nblocks + L] = acc;
         TV_SMALL_MARK(3);
@@ -570,8 +589,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_reg(DG g, WT<T> w, 
     n.h_pt = ok && g.ta && (t > 0);
     const bool has_tail = ok && (col0 + V < g.nx), has_head = ok && (col0 > 0);
     const unsigned b0 = (unsigned)(offx * EB);
-    const int d_row = g.rp * (int)EB, d_frame = (int)(g.s_t * EB), d_plane = (int)(g.s_z * EB);
-    auto at = [&](bool valid, unsigned base, int delta) -> unsigned { return valid ? base + (unsigned)delta : kOOB; };
+    const SmallDeltas bd = small_deltas<T>(g);
     Vec<T, V> x = ok ? vload<T, V>(a.xa + offx) : zero;
     const Vec<T, V> x0 = ok ? vload<T, V>(a.x0 + offx) : zero;
     const Vec<T, V> mf = (ok && g.ta) ? mask_factor<T, V>(g, w.sf, y, col0) : vsplat<T, V>(T(1));
@@ -582,13 +600,8 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_reg(DG g, WT<T> w, 
         unsigned b = b0;
         asm volatile("" : "+v"(b));
         // ---- pass 1: 1 / |D x|, TV(x) (pytv/tv_GPU.py:84-88)
-        n.c = x;
-        n.nr = coh_ldv<T, V>(mxc, at(NEXT && n.h_nr, b, d_row)); n.pr = coh_ldv<T, V>(mxc, at(PREV && n.h_pr, b, -d_row));
-        n.nz = coh_ldv<T, V>(mxc, at(NEXT && n.h_nz, b, d_plane)); n.pz = coh_ldv<T, V>(mxc, at(PREV && n.h_pz, b, -d_plane));
-        n.nt = coh_ldv<T, V>(mxc, at(NEXT && n.h_nt, b, d_frame)); n.pt = coh_ldv<T, V>(mxc, at(PREV && n.h_pt, b, -d_frame));
-        const T x_tail = coh_ld1<T>(mxc, at(has_tail, b, V * (int)EB)), x_head = coh_ld1<T>(mxc, at(has_head, b, -(int)EB));
-        n.nc = shift_left<T, V>(x, x_tail);
-        n.pc = shift_right<T, V>(x, x_head);
+        T x_head, x_tail;
+        coh_neighbours<NEXT, PREV>(mxc, b, bd, has_head, has_tail, x, n, x_head, x_tail);
         double acc = 0.0;
         Vec<T, V> nv;
         {
@@ -603,17 +616,17 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_reg(DG g, WT<T> w, 
             }
             if (!ok) acc = 0.0;
         }
-        coh_stv<T, V>(mn, at(ok, b, 0), nv);
+        coh_stv<T, V>(mn, coh_at(ok, b, 0), nv);
         acc = block_sum(acc, sm);
         if (threadIdx.x == 0) a.partials[((long long)it * 2 + 0) * sp.nblocks + L] = acc;
         if (small_sync(a.flags, L, dep, e0 + (unsigned)(2 * it + 1), &sh_abort)) break;
         // ---- pass 2: G from x and 1 / |D x| (pytv/tv_GPU.py:91-124), x <- x - step ((x - x0) + lambda G) (README.md:122-123)
         asm volatile("" : "+v"(b));
         ns.c = nv;
-        ns.nr = coh_ldv<T, V>(mn, at(n.h_nr, b, d_row)); ns.pr = coh_ldv<T, V>(mn, at(n.h_pr, b, -d_row));
-        ns.nz = coh_ldv<T, V>(mn, at(n.h_nz, b, d_plane)); ns.pz = coh_ldv<T, V>(mn, at(n.h_pz, b, -d_plane));
-        ns.nt = coh_ldv<T, V>(mn, at(n.h_nt, b, d_frame)); ns.pt = coh_ldv<T, V>(mn, at(n.h_pt, b, -d_frame));
-        const T n_tail = coh_ld1<T>(mn, at(has_tail, b, V * (int)EB)), n_head = coh_ld1<T>(mn, at(has_head, b, -(int)EB));
+        ns.nr = coh_ldv<T, V>(mn, coh_at(n.h_nr, b, bd.row)); ns.pr = coh_ldv<T, V>(mn, coh_at(n.h_pr, b, -bd.row));
+        ns.nz = coh_ldv<T, V>(mn, coh_at(n.h_nz, b, bd.plane)); ns.pz = coh_ldv<T, V>(mn, coh_at(n.h_pz, b, -bd.plane));
+        ns.nt = coh_ldv<T, V>(mn, coh_at(n.h_nt, b, bd.frame)); ns.pt = coh_ldv<T, V>(mn, coh_at(n.h_pt, b, -bd.frame));
+        const T n_tail = coh_ld1<T>(mn, coh_at(has_tail, b, V * (int)EB)), n_head = coh_ld1<T>(mn, coh_at(has_head, b, -(int)EB));
         ns.nc = shift_left<T, V>(nv, n_tail);
         ns.pc = shift_right<T, V>(nv, n_head);
         Vec<T, V> G;
@@ -623,10 +636,10 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_reg(DG g, WT<T> w, 
             // central: G(p) = 1/2 sum_a [ g_a(p-e) - g_a(p+e) ], g_a(q) = 1/2 w_a (x(q+e) - x(q-e)) / |D x|(q) at interior q: x two steps away, 1/|Dx| one
             // step away (the expressions of sg_site_central, tv_site.h); two-point z / t axes: the forward stencil on the neighbours of pass 1
             const T hh = T(0.5);
-            const Vec<T, V> xm2r = coh_ldv<T, V>(mxc, at(ok && y >= 2, b, -2 * d_row)), xp2r = coh_ldv<T, V>(mxc, at(ok && y + 2 < g.ny, b, 2 * d_row));
-            const Vec<T, V> xm2z = coh_ldv<T, V>(mxc, at(ok && g.za && zl >= 2, b, -2 * d_plane)), xp2z = coh_ldv<T, V>(mxc, at(ok && g.za && zl + 2 < g.nz, b, 2 * d_plane));
-            const Vec<T, V> xm2t = coh_ldv<T, V>(mxc, at(ok && g.ta && t >= 2, b, -2 * d_frame)), xp2t = coh_ldv<T, V>(mxc, at(ok && g.ta && t + 2 < g.m, b, 2 * d_frame));
-            const T x_head2 = coh_ld1<T>(mxc, at(ok && col0 >= 2, b, -2 * (int)EB)), x_tail2 = coh_ld1<T>(mxc, at(ok && col0 + V + 1 < g.nx, b, (V + 1) * (int)EB));
+            const Vec<T, V> xm2r = coh_ldv<T, V>(mxc, coh_at(ok && y >= 2, b, -2 * bd.row)), xp2r = coh_ldv<T, V>(mxc, coh_at(ok && y + 2 < g.ny, b, 2 * bd.row));
+            const Vec<T, V> xm2z = coh_ldv<T, V>(mxc, coh_at(ok && g.za && zl >= 2, b, -2 * bd.plane)), xp2z = coh_ldv<T, V>(mxc, coh_at(ok && g.za && zl + 2 < g.nz, b, 2 * bd.plane));
+            const Vec<T, V> xm2t = coh_ldv<T, V>(mxc, coh_at(ok && g.ta && t >= 2, b, -2 * bd.frame)), xp2t = coh_ldv<T, V>(mxc, coh_at(ok && g.ta && t + 2 < g.m, b, 2 * bd.frame));
+            const T x_head2 = coh_ld1<T>(mxc, coh_at(ok && col0 >= 2, b, -2 * (int)EB)), x_tail2 = coh_ld1<T>(mxc, coh_at(ok && col0 + V + 1 < g.nx, b, (V + 1) * (int)EB));
             const Vec<T, V>& xc = n.c;
             Vec<T, V> r = zero;
             auto cen = [&](int pos, int cnt, const Vec<T, V>& xm2, const Vec<T, V>& xp2, const Vec<T, V>& nm1, const Vec<T, V>& np1, T wa, bool weighted, bool timeax) {
@@ -693,7 +706,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_reg(DG g, WT<T> w, 
         }
         zero_pad_cols<T, V>(g, col0, x);
         if (!ok) acc = 0.0;
-        coh_stv<T, V>(mxo, at(ok, b, 0), x);
+        coh_stv<T, V>(mxo, coh_at(ok, b, 0), x);
         acc = block_sum(acc, sm);
         if (threadIdx.x == 0) a.partials[((long long)it * 2 + 1) * sp.nblocks + L] = acc;
         if (it + 1 < a.n_iter && small_sync(a.flags, L, dep, e0 + (unsigned)(2 * it + 2), &sh_abort)) break;
@@ -723,14 +736,13 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_flat(DG g, WT<T> w,
     const int t = fid.t, zl = fid.zl;
     const CohMem mx = CohMem::make(a.x, a.x_bytes), mq = CohMem::make(a.q, a.q_bytes);
     const Vec<T, V> zero = vsplat<T, V>(T(0));
-    const int d_row = g.rp * (int)EB, d_frame = (int)(g.s_t * EB), d_plane = (int)(g.s_z * EB), d_qplane = (int)(g.s_dz * EB);
+    const SmallDeltas bd = small_deltas<T>(g);
     int dq[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) dq[k] = -1;
     for_each_channel<S>(g, [&](auto slot, int ch) {
         if constexpr (decltype(slot)::value < NS) dq[decltype(slot)::value] = (int)((long long)ch * g.s_z * EB);
     });
-    auto at = [&](bool valid, unsigned base, int delta) -> unsigned { return valid ? base + (unsigned)delta : kOOB; };
     constexpr int U_R = 0, U_C = 1, U_Z = (S == HYBRID) ? 4 : 2, U_T = (S == HYBRID) ? 6 : 3;
     constexpr int D_R = (S == HYBRID) ? 2 : 0, D_C = (S == HYBRID) ? 3 : 1, D_Z = (S == HYBRID) ? 5 : 2, D_T = (S == HYBRID) ? 7 : 3;
     constexpr bool LO = (S != DOWNWIND), HI = (S != UPWIND), NEXT = (S != DOWNWIND), PREV = (S != UPWIND);
@@ -772,16 +784,11 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_flat(DG g, WT<T> w,
             XN<T, V> n;
             const Site s = site(j, n);
             const Vec<T, V> mf = mfs[j < kFlatMaxSites ? j : 0];
-            n.c = coh_ldv<T, V>(mx, at(s.ok, s.bx, 0));
-            n.nr = coh_ldv<T, V>(mx, at(NEXT && n.h_nr, s.bx, d_row)); n.pr = coh_ldv<T, V>(mx, at(PREV && n.h_pr, s.bx, -d_row));
-            n.nz = coh_ldv<T, V>(mx, at(NEXT && n.h_nz, s.bx, d_plane)); n.pz = coh_ldv<T, V>(mx, at(PREV && n.h_pz, s.bx, -d_plane));
-            n.nt = coh_ldv<T, V>(mx, at(NEXT && n.h_nt, s.bx, d_frame)); n.pt = coh_ldv<T, V>(mx, at(PREV && n.h_pt, s.bx, -d_frame));
-            const T x_tail = coh_ld1<T>(mx, at(NEXT && s.has_tail, s.bx, V * (int)EB)), x_head = coh_ld1<T>(mx, at(PREV && s.has_head, s.bx, -(int)EB));
+            T x_head, x_tail;
+            coh_neighbours<NEXT, PREV>(mx, s.bx, bd, s.has_head, s.has_tail, coh_ldv<T, V>(mx, coh_at(s.ok, s.bx, 0)), n, x_head, x_tail);
             Vec<T, V> q[NS];
 #pragma unroll
-            for (int k = 0; k < NS; ++k) q[k] = coh_ldv<T, V>(mq, at(s.ok && dq[k] >= 0, s.bq, dq[k]));
-            n.nc = NEXT ? shift_left<T, V>(n.c, x_tail) : zero;
-            n.pc = PREV ? shift_right<T, V>(n.c, x_head) : zero;
+            for (int k = 0; k < NS; ++k) q[k] = coh_ldv<T, V>(mq, coh_at(s.ok && dq[k] >= 0, s.bq, dq[k]));
             Vec<T, V> o[8];
             d_slots<S, T, V>(g, w, n, mf, o);
             Vec<T, V> vs = zero;
@@ -799,7 +806,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_flat(DG g, WT<T> w,
                 scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * a.inv_lambda);
             }
 #pragma unroll
-            for (int k = 0; k < NS; ++k) coh_stv<T, V>(mq, at(s.ok && dq[k] >= 0, s.bq, dq[k]), q[k] * scale);
+            for (int k = 0; k < NS; ++k) coh_stv<T, V>(mq, coh_at(s.ok && dq[k] >= 0, s.bq, dq[k]), q[k] * scale);
             if (s.ok) acc += part;
         }
         acc = block_sum(acc, sm);
@@ -814,12 +821,12 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_flat(DG g, WT<T> w,
             const int y = s.y, col0 = s.col0;
             Vec<T, V> q[NS];
 #pragma unroll
-            for (int k = 0; k < NS; ++k) q[k] = coh_ldv<T, V>(mq, at(s.ok && dq[k] >= 0, s.bq, dq[k]));
-            const Vec<T, V> lo_r = coh_ldv<T, V>(mq, at(LO && n.h_pr, s.bq, dq[U_R] - d_row)), hi_r = coh_ldv<T, V>(mq, at(HI && n.h_nr, s.bq, dq[D_R] + d_row));
-            const Vec<T, V> lo_z = coh_ldv<T, V>(mq, at(LO && n.h_pz, s.bq, dq[U_Z] - d_qplane)), hi_z = coh_ldv<T, V>(mq, at(HI && n.h_nz, s.bq, dq[D_Z] + d_qplane));
-            const Vec<T, V> lo_t = coh_ldv<T, V>(mq, at(LO && n.h_pt, s.bq, dq[U_T] - d_frame)), hi_t = coh_ldv<T, V>(mq, at(HI && n.h_nt, s.bq, dq[D_T] + d_frame));
-            const T q_head = coh_ld1<T>(mq, at(LO && s.has_head, s.bq, dq[U_C] - (int)EB)), q_tail = coh_ld1<T>(mq, at(HI && s.has_tail, s.bq, dq[D_C] + V * (int)EB));
-            Vec<T, V> x = coh_ldv<T, V>(mx, at(s.ok, s.bx, 0));
+            for (int k = 0; k < NS; ++k) q[k] = coh_ldv<T, V>(mq, coh_at(s.ok && dq[k] >= 0, s.bq, dq[k]));
+            const Vec<T, V> lo_r = coh_ldv<T, V>(mq, coh_at(LO && n.h_pr, s.bq, dq[U_R] - bd.row)), hi_r = coh_ldv<T, V>(mq, coh_at(HI && n.h_nr, s.bq, dq[D_R] + bd.row));
+            const Vec<T, V> lo_z = coh_ldv<T, V>(mq, coh_at(LO && n.h_pz, s.bq, dq[U_Z] - bd.qplane)), hi_z = coh_ldv<T, V>(mq, coh_at(HI && n.h_nz, s.bq, dq[D_Z] + bd.qplane));
+            const Vec<T, V> lo_t = coh_ldv<T, V>(mq, coh_at(LO && n.h_pt, s.bq, dq[U_T] - bd.frame)), hi_t = coh_ldv<T, V>(mq, coh_at(HI && n.h_nt, s.bq, dq[D_T] + bd.frame));
+            const T q_head = coh_ld1<T>(mq, coh_at(LO && s.has_head, s.bq, dq[U_C] - (int)EB)), q_tail = coh_ld1<T>(mq, coh_at(HI && s.has_tail, s.bq, dq[D_C] + V * (int)EB));
+            Vec<T, V> x = coh_ldv<T, V>(mx, coh_at(s.ok, s.bx, 0));
             const long long offx = (long long)(s.bx / EB);
             const Vec<T, V> x0 = s.ok ? vload<T, V>(a.x0 + offx) : zero;
             Vec<T, V> p = s.ok ? vload<T, V>(a.p + offx) : zero;
@@ -885,7 +892,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_cp_flat(DG g, WT<T> w,
                 const double e = (double)x.v[i] - (double)x0.v[i];
                 part += 0.5 * e * e;
             }
-            coh_stv<T, V>(mx, at(s.ok, s.bx, 0), x);
+            coh_stv<T, V>(mx, coh_at(s.ok, s.bx, 0), x);
             if (s.ok) { vstore<T, V>(a.p + offx, p); acc += part; }
         }
         acc = block_sum(acc, sm);
@@ -910,8 +917,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_flat(DG g, WT<T> w,
     const CohMem mxa = CohMem::make((const T*)a.xa, a.x_bytes), mxb = CohMem::make((const T*)a.xb, a.x_bytes);
     const CohMem mn = CohMem::make((const T*)a.norms_ext + g.s_z, a.n_bytes - g.s_z * (long long)EB);
     const Vec<T, V> zero = vsplat<T, V>(T(0));
-    const int d_row = g.rp * (int)EB, d_frame = (int)(g.s_t * EB), d_plane = (int)(g.s_z * EB);
-    auto at = [&](bool valid, unsigned base, int delta) -> unsigned { return valid ? base + (unsigned)delta : kOOB; };
+    const SmallDeltas bd = small_deltas<T>(g);
     Vec<T, V> mfs[kFlatMaxSites];
 #pragma unroll
     for (int j = 0; j < kFlatMaxSites; ++j) {
@@ -938,15 +944,6 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_flat(DG g, WT<T> w,
         s.has_head = s.ok && (s.col0 > 0);
         return s;
     };
-    // the eight neighbours of an image-like array around site s (absent ones: out of range -> 0)
-    auto neighbours = [&](const CohMem& m, const Site& s, XN<T, V>& n, const Vec<T, V>& c, T& head, T& tail) {
-        n.c = c;
-        n.nr = coh_ldv<T, V>(m, at(n.h_nr, s.b, d_row)); n.pr = coh_ldv<T, V>(m, at(n.h_pr, s.b, -d_row));
-        n.nz = coh_ldv<T, V>(m, at(n.h_nz, s.b, d_plane)); n.pz = coh_ldv<T, V>(m, at(n.h_pz, s.b, -d_plane));
-        n.nt = coh_ldv<T, V>(m, at(n.h_nt, s.b, d_frame)); n.pt = coh_ldv<T, V>(m, at(n.h_pt, s.b, -d_frame));
-        tail = coh_ld1<T>(m, at(s.has_tail, s.b, V * (int)EB));
-        head = coh_ld1<T>(m, at(s.has_head, s.b, -(int)EB));
-    };
     for (int it = 0; it < a.n_iter; ++it) {
         const CohMem& mxc = (it & 1) ? mxb : mxa;
         const CohMem& mxo = (it & 1) ? mxa : mxb;
@@ -956,11 +953,9 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_flat(DG g, WT<T> w,
             XN<T, V> n;
             const Site s = site(j, n);
             const Vec<T, V> mf = mfs[j < kFlatMaxSites ? j : 0];
-            const Vec<T, V> x = coh_ldv<T, V>(mxc, at(s.ok, s.b, 0));
+            const Vec<T, V> x = coh_ldv<T, V>(mxc, coh_at(s.ok, s.b, 0));
             T x_head, x_tail;
-            neighbours(mxc, s, n, x, x_head, x_tail);
-            n.nc = shift_left<T, V>(x, x_tail);
-            n.pc = shift_right<T, V>(x, x_head);
+            coh_neighbours<true, true>(mxc, s.b, bd, s.has_head, s.has_tail, x, n, x_head, x_tail);
             Vec<T, V> o[8], nv;
             d_slots<S, T, V>(g, w, n, mf, o);
             const Vec<T, V> ssq = sumsq_slots<T, V>(o);
@@ -971,7 +966,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_flat(DG g, WT<T> w,
                 part += (double)r;
                 nv.v[i] = (ssq.v[i] >= tiny_sumsq<T>()) ? T(1) / r : T(0);
             }
-            coh_stv<T, V>(mn, at(s.ok, s.b, 0), nv);
+            coh_stv<T, V>(mn, coh_at(s.ok, s.b, 0), nv);
             if (s.ok) acc += part;
         }
         acc = block_sum(acc, sm);
@@ -987,26 +982,23 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_flat(DG g, WT<T> w,
             const int y = s.y, col0 = s.col0;
             const unsigned b = s.b;
             const bool ok = s.ok;
-            Vec<T, V> x = coh_ldv<T, V>(mxc, at(ok, b, 0));
-            const Vec<T, V> nv = coh_ldv<T, V>(mn, at(ok, b, 0));
+            Vec<T, V> x = coh_ldv<T, V>(mxc, coh_at(ok, b, 0));
+            const Vec<T, V> nv = coh_ldv<T, V>(mn, coh_at(ok, b, 0));
             T x_head, x_tail, n_head, n_tail;
-            neighbours(mxc, s, n, x, x_head, x_tail);
-            neighbours(mn, s, nn, nv, n_head, n_tail);
+            coh_neighbours<true, true>(mxc, b, bd, s.has_head, s.has_tail, x, n, x_head, x_tail);
+            coh_neighbours<true, true>(mn, b, bd, s.has_head, s.has_tail, nv, nn, n_head, n_tail);
             const Vec<T, V> x0 = ok ? vload<T, V>(a.x0 + (long long)(b / EB)) : zero;
-            n.nc = shift_left<T, V>(x, x_tail);
-            n.pc = shift_right<T, V>(x, x_head);
-            nn.nc = shift_left<T, V>(nv, n_tail);
-            nn.pc = shift_right<T, V>(nv, n_head);
             const XN<T, V>& ns_ = nn;
             Vec<T, V> G;
             if constexpr (S != CENTRAL) {
                 G = subgrad_site<S, T, V>(g, w, n, ns_, mf);
             } else {
                 const T hh = T(0.5);
-                const Vec<T, V> xm2r = coh_ldv<T, V>(mxc, at(ok && y >= 2, b, -2 * d_row)), xp2r = coh_ldv<T, V>(mxc, at(ok && y + 2 < g.ny, b, 2 * d_row));
-                const Vec<T, V> xm2z = coh_ldv<T, V>(mxc, at(ok && g.za && zl >= 2, b, -2 * d_plane)), xp2z = coh_ldv<T, V>(mxc, at(ok && g.za && zl + 2 < g.nz, b, 2 * d_plane));
-                const Vec<T, V> xm2t = coh_ldv<T, V>(mxc, at(ok && g.ta && t >= 2, b, -2 * d_frame)), xp2t = coh_ldv<T, V>(mxc, at(ok && g.ta && t + 2 < g.m, b, 2 * d_frame));
-                const T x_head2 = coh_ld1<T>(mxc, at(ok && col0 >= 2, b, -2 * (int)EB)), x_tail2 = coh_ld1<T>(mxc, at(ok && col0 + V + 1 < g.nx, b, (V + 1) * (int)EB));
+                const Vec<T, V> xm2r = coh_ldv<T, V>(mxc, coh_at(ok && y >= 2, b, -2 * bd.row)), xp2r = coh_ldv<T, V>(mxc, coh_at(ok && y + 2 < g.ny, b, 2 * bd.row));
+                const Vec<T, V> xm2z = coh_ldv<T, V>(mxc, coh_at(ok && g.za && zl >= 2, b, -2 * bd.plane));
+                const Vec<T, V> xp2z = coh_ldv<T, V>(mxc, coh_at(ok && g.za && zl + 2 < g.nz, b, 2 * bd.plane));
+                const Vec<T, V> xm2t = coh_ldv<T, V>(mxc, coh_at(ok && g.ta && t >= 2, b, -2 * bd.frame)), xp2t = coh_ldv<T, V>(mxc, coh_at(ok && g.ta && t + 2 < g.m, b, 2 * bd.frame));
+                const T x_head2 = coh_ld1<T>(mxc, coh_at(ok && col0 >= 2, b, -2 * (int)EB)), x_tail2 = coh_ld1<T>(mxc, coh_at(ok && col0 + V + 1 < g.nx, b, (V + 1) * (int)EB));
                 const Vec<T, V>& xc = n.c;
                 Vec<T, V> r = zero;
                 auto cen = [&](int pos, int cnt, const Vec<T, V>& xm2, const Vec<T, V>& xp2, const Vec<T, V>& nm1, const Vec<T, V>& np1, T wa, bool weighted, bool timeax) {
@@ -1072,7 +1064,7 @@ __global__ __launch_bounds__(kRegMaxThreads) void k_small_sg_flat(DG g, WT<T> w,
                 part += 0.5 * e * e;
             }
             zero_pad_cols<T, V>(g, col0, x);
-            coh_stv<T, V>(mxo, at(ok, b, 0), x);
+            coh_stv<T, V>(mxo, coh_at(ok, b, 0), x);
             if (ok) acc += part;
         }
         acc = block_sum(acc, sm);
@@ -1224,12 +1216,52 @@ static bool small_plan_flat(const DG& d, int V, const void* kernel, SmallPlan& s
 
 static long long small_max_voxels() { return 1024ll * env_int("TV_SMALL_MAX_KVOXELS", 4096); }
 
+// the volumes the persistent kernels take: at most TV_SMALL_MAX_KVOXELS, every array below 2^31 bytes (kOOB, 32-bit buffer offsets)
+static bool small_fits(const tv_geom* g, const DG& d) {
+    const long long eb = (g->dtype == TV_F32) ? 4 : 8;
+    return d.s_z * d.nz <= small_max_voxels() && d.s_dz * (d.nz + 2) * eb < (1ll << 31);
+}
+
 static int small_check(const tv_geom* g, DG& d, const char* who) {
     if (int rc = make_dg(g, d, true)) return rc;
     if (g->z0 != 0 || g->nz != g->nz_global) return fail(TV_E_ARG, "the persistent small-volume kernels take an unsharded volume (nz == nz_global)");
-    const long long eb = (g->dtype == TV_F32) ? 4 : 8;
-    if (d.s_z * d.nz > small_max_voxels() || d.s_dz * (d.nz + 2) * eb >= (1ll << 31))
-        return fail(TV_E_ARG, who);
+    if (!small_fits(g, d)) return fail(TV_E_ARG, (std::string(who) + ": volume too large for the persistent kernel (tv_small_supported)").c_str());
+    return 0;
+}
+
+// workspace: the flags (one 128-byte line per launched block, + the line that holds the epoch), then the partials
+static size_t small_flag_bytes() { return (size_t)(kMaxSmallBlocks + 1) * kFlagStride * sizeof(unsigned); }
+
+// one call of a persistent loop: pick the form, split the workspace, launch cooperatively, reduce the partials into hist
+template <typename T, typename Args>
+static int small_launch(const DG& d, int V, WT<T> w, Args a, const void* reg_kern, const void* flat_kern, const void* generic_kern, double* hist,
+                        int64_t hist_stride, int64_t hist_fid_offset, void* ws, hipStream_t st, const char* who) {
+    const void* kern = reg_kern;
+    SmallPlan sp;
+    int threads = kSmallThreads;
+    // TV_SMALL_SITES: 0 = resident form first, then the streamed form with 2 .. 4 site-vectors per thread; 1 = resident only; 2 .. 4 = streamed from there
+    const int s0 = env_int("TV_SMALL_SITES", 0);
+    bool flat = s0 <= 1 && small_plan_flat(d, V, kern, sp, threads);
+    for (int sites = s0 > 2 ? s0 : 2; !flat && sites <= kFlatMaxSites && s0 != 1; ++sites) {
+        kern = flat_kern;
+        flat = small_plan_flat(d, V, kern, sp, threads, sites);
+    }
+    if (!flat) {
+        kern = generic_kern;
+        threads = kSmallThreads;
+        const int cap = small_capacity(kern);
+        if (cap < 8) return fail(TV_E_ARG, (std::string(who) + ": no HIP device / occupancy query failed").c_str());
+        sp = small_plan(d, V, cap);
+    }
+    if (sp.grid > kMaxSmallBlocks) return fail(TV_E_ARG, "internal: more blocks than the workspace holds");
+    a.flags = (unsigned*)ws;
+    a.partials = (double*)((char*)ws + small_flag_bytes());
+    DG dd = d;
+    void* args[] = {&dd, &w, &sp, &a};
+    HIP_TRY(hipLaunchCooperativeKernel(kern, dim3((unsigned)sp.grid), dim3((unsigned)threads), args, 0, st));
+    hipLaunchKernelGGL(k_small_reduce, dim3((unsigned)(2 * a.n_iter)), dim3(256), 0, st, (const double*)a.partials, sp.nblocks, hist, (long long)hist_stride,
+                       (long long)hist_fid_offset, a.flags, (unsigned)(2 * a.n_iter));
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -1243,8 +1275,7 @@ int tv_small_supported(const tv_geom* g) {
     DG d;
     if (make_dg(g, d, true)) return 0;
     if (g->z0 != 0 || g->nz != g->nz_global) return 0;
-    const long long eb = (g->dtype == TV_F32) ? 4 : 8;
-    if (d.s_z * d.nz > small_max_voxels() || d.s_dz * (d.nz + 2) * eb >= (1ll << 31)) return 0;
+    if (!small_fits(g, d)) return 0;
     if (env_int("TV_NO_SMALL", 0)) return 0;
     return 1;
 }
@@ -1252,102 +1283,46 @@ int tv_small_supported(const tv_geom* g) {
 size_t tv_small_workspace_bytes(const tv_geom* g, int64_t n_iter) {
     DG d;
     if (make_dg(g, d, true) || n_iter < 1) return 0;
-    // flags: one 128-byte line per launched block; partials: n_iter x 2 x blocks doubles
+    // partials: n_iter x 2 x blocks doubles
     const size_t blocks = kMaxSmallBlocks;
-    const size_t flag_bytes = (blocks + 1) * kFlagStride * sizeof(unsigned);      // (+ the line that holds the epoch)
 #ifdef TV_SMALL_PROFILE
-    return flag_bytes + (size_t)n_iter * 7 * blocks * sizeof(double) + 256;
+    return small_flag_bytes() + (size_t)n_iter * 7 * blocks * sizeof(double) + 256;
 #else
-    return flag_bytes + (size_t)n_iter * 2 * blocks * sizeof(double) + 256;
+    return small_flag_bytes() + (size_t)n_iter * 2 * blocks * sizeof(double) + 256;
 #endif
 }
 
 int tv_small_cp(const tv_geom* g, void* x, const void* x0, void* p, void* q, double sigma_D, double lambda, double tau, double sigma_A,
                 int64_t n_iter, double* hist, int64_t hist_stride, int64_t hist_fid_offset, void* ws, void* stream) {
     DG d;
-    if (int rc = small_check(g, d, "tv_small_cp: volume too large for the persistent kernel (tv_small_supported)")) return rc;
+    if (int rc = small_check(g, d, "tv_small_cp")) return rc;
     if (x == nullptr || x0 == nullptr || p == nullptr || q == nullptr || hist == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
     if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
     if (n_iter < 1 || n_iter > (1 << 20)) return fail(TV_E_ARG, "n_iter out of range");
     if (hist_stride < 1 || hist_fid_offset == 0 || hist_fid_offset >= hist_stride || hist_fid_offset < 0) return fail(TV_E_ARG, "hist_stride / hist_fid_offset: 0 < fid_offset < stride");
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x0, p, q, d.wv});
-    hipStream_t st = (hipStream_t)stream;
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        const void* kern = (const void*)k_small_cp_reg<S, T, V>;
-        SmallPlan sp;
-        int threads = kSmallThreads;
-        // TV_SMALL_SITES: 0 = resident form first, then the streamed form with 2 .. 4 site-vectors per thread; 1 = resident only; 2 .. 4 = streamed from there
-        const int s0 = env_int("TV_SMALL_SITES", 0);
-        bool flat = s0 <= 1 && small_plan_flat(d, V, kern, sp, threads);
-        for (int sites = s0 > 2 ? s0 : 2; !flat && sites <= kFlatMaxSites && s0 != 1; ++sites) {
-            kern = (const void*)k_small_cp_flat<S, T, V>;
-            flat = small_plan_flat(d, V, kern, sp, threads, sites);
-        }
-        if (!flat) {
-            kern = (const void*)k_small_cp<S, T, V>;
-            threads = kSmallThreads;
-            const int cap = small_capacity(kern);
-            if (cap < 8) return fail(TV_E_ARG, "tv_small_cp: no HIP device / occupancy query failed");
-            sp = small_plan(d, V, cap);
-        }
-        if (sp.grid > kMaxSmallBlocks) return fail(TV_E_ARG, "internal: more blocks than the workspace holds");
-        unsigned* flags = (unsigned*)ws;
-        double* partials = (double*)((char*)ws + (size_t)(kMaxSmallBlocks + 1) * kFlagStride * sizeof(unsigned));
-        DG dd = d;
-        WT<T> w = make_w<T>(g);
         SmallCpArgs<T> a{(T*)x, (const T*)x0, (T*)p, (T*)q, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), (int)n_iter,
-                         flags, partials, d.s_z * d.nz * (long long)sizeof(T), d.s_dz * d.nz * (long long)sizeof(T)};
-        void* args[] = {&dd, &w, &sp, &a};
-        HIP_TRY(hipLaunchCooperativeKernel(kern, dim3((unsigned)sp.grid), dim3((unsigned)threads), args, 0, st));
-        hipLaunchKernelGGL(k_small_reduce, dim3((unsigned)(2 * n_iter)), dim3(256), 0, st, (const double*)partials, sp.nblocks, hist, (long long)hist_stride,
-                           (long long)hist_fid_offset, flags, (unsigned)(2 * n_iter));
-        HIP_TRY(hipGetLastError());
-        return 0;
+                         nullptr, nullptr, d.s_z * d.nz * (long long)sizeof(T), d.s_dz * d.nz * (long long)sizeof(T)};
+        return small_launch(d, V, make_w<T>(g), a, (const void*)k_small_cp_reg<S, T, V>, (const void*)k_small_cp_flat<S, T, V>, (const void*)k_small_cp<S, T, V>,
+                            hist, hist_stride, hist_fid_offset, ws, (hipStream_t)stream, "tv_small_cp");
     });
 }
 
 int tv_small_subgrad_descent(const tv_geom* g, void* x, void* x_alt, const void* x0, void* norms_ext, double step, double lambda, int64_t n_iter,
                              double* hist, int64_t hist_stride, int64_t hist_fid_offset, void* ws, void* stream) {
     DG d;
-    if (int rc = small_check(g, d, "tv_small_subgrad_descent: volume too large for the persistent kernel (tv_small_supported)")) return rc;
+    if (int rc = small_check(g, d, "tv_small_subgrad_descent")) return rc;
     if (x == nullptr || x_alt == nullptr || x0 == nullptr || norms_ext == nullptr || hist == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
     if (x == x_alt) return fail(TV_E_ARG, "x and x_alt must be different arrays (the iterate is ping-ponged)");
     if (n_iter < 1 || n_iter > (1 << 20)) return fail(TV_E_ARG, "n_iter out of range");
     if (hist_stride < 1 || hist_fid_offset == 0 || hist_fid_offset >= hist_stride || hist_fid_offset < 0) return fail(TV_E_ARG, "hist_stride / hist_fid_offset: 0 < fid_offset < stride");
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_alt, x0, norms_ext, d.wv});
-    hipStream_t st = (hipStream_t)stream;
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        const void* kern = nullptr;
-        SmallPlan sp;
-        int threads = kSmallThreads;
-        bool flat = false;
-        kern = (const void*)k_small_sg_reg<S, T, V>;
-        const int s0 = env_int("TV_SMALL_SITES", 0);
-        flat = s0 <= 1 && small_plan_flat(d, V, kern, sp, threads);
-        for (int sites = s0 > 2 ? s0 : 2; !flat && sites <= kFlatMaxSites && s0 != 1; ++sites) {
-            kern = (const void*)k_small_sg_flat<S, T, V>;
-            flat = small_plan_flat(d, V, kern, sp, threads, sites);
-        }
-        if (!flat) {
-            kern = (const void*)k_small_sg<S, T, V>;
-            threads = kSmallThreads;
-            const int cap = small_capacity(kern);
-            if (cap < 8) return fail(TV_E_ARG, "tv_small_subgrad_descent: no HIP device / occupancy query failed");
-            sp = small_plan(d, V, cap);
-        }
-        if (sp.grid > kMaxSmallBlocks) return fail(TV_E_ARG, "internal: more blocks than the workspace holds");
-        unsigned* flags = (unsigned*)ws;
-        double* partials = (double*)((char*)ws + (size_t)(kMaxSmallBlocks + 1) * kFlagStride * sizeof(unsigned));
-        DG dd = d;
-        WT<T> w = make_w<T>(g);
-        SmallSgArgs<T> a{(T*)x, (T*)x_alt, (const T*)x0, (T*)norms_ext, (T)step, (T)lambda, (int)n_iter, flags, partials,
+        SmallSgArgs<T> a{(T*)x, (T*)x_alt, (const T*)x0, (T*)norms_ext, (T)step, (T)lambda, (int)n_iter, nullptr, nullptr,
                          d.s_z * d.nz * (long long)sizeof(T), d.s_z * (d.nz + 2) * (long long)sizeof(T)};
-        void* args[] = {&dd, &w, &sp, &a};
-        HIP_TRY(hipLaunchCooperativeKernel(kern, dim3((unsigned)sp.grid), dim3((unsigned)threads), args, 0, st));
-        hipLaunchKernelGGL(k_small_reduce, dim3((unsigned)(2 * n_iter)), dim3(256), 0, st, (const double*)partials, sp.nblocks, hist, (long long)hist_stride,
-                           (long long)hist_fid_offset, flags, (unsigned)(2 * n_iter));
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return small_launch(d, V, make_w<T>(g), a, (const void*)k_small_sg_reg<S, T, V>, (const void*)k_small_sg_flat<S, T, V>, (const void*)k_small_sg<S, T, V>,
+                            hist, hist_stride, hist_fid_offset, ws, (hipStream_t)stream, "tv_small_subgrad_descent");
     });
 }
 

@@ -353,13 +353,29 @@ int tv_subgrad_step(const tv_geom* g, void* x, const void* x0, const void* G, do
  *   tv_small_subgrad_descent : n_iter iterations of  x <- x - step ((x - x0) + lambda G(x))  (tv_subgrad + tv_subgrad_step's
  *                              arithmetic); the iterate is ping-ponged between x and x_alt: after an ODD n_iter the result is in
  *                              x_alt, after an even one in x; norms_ext: (nz + 2) planes of scratch (1 / |D x|);
- *                              hist as above: TV(x_k) and 1/2 |x_{k+1} - x0|^2 */
+ *                              hist as above: TV(x_k) and 1/2 |x_{k+1} - x0|^2
+ *   tv_small_admm            : n_outer outer iterations of scaled-form ADMM whose x-solve is n_cheb (1 .. 32) Chebyshev steps -- what
+ *                              tv_DT_axpy + tv_normal_op2 + tv_cheb_step + tv_admm_tu compute per outer iteration:
+ *                                r = x0 - x + rho D^T (t - D x);  e_{k+1} = e_k + alpha_k (r - (I + rho D^T D) e_k) + beta_k (e_k - e_{k-1}),
+ *                                e_0 = e_{-1} = 0, k = 0 .. n_cheb-1;  x <- x + e_{n_cheb};
+ *                                z = shrink(D x + u, thresh);  u <- u + D x - z;  t <- z - u
+ *                              alpha / beta: HOST arrays of n_cheb coefficients (they follow from the spectral interval [1, 1 + rho L] alone).
+ *                              STATE, updated in place: x, t (= z - u, a gradient array) and u (a gradient array), as the ordinary
+ *                              single-reduction path keeps them -- calls can be mixed with tv_admm_tu based iterations.  SCRATCH, contents
+ *                              undefined on entry and exit: r, e_a, e_b (images) and grad (a gradient array); all eight arrays differ.
+ *                              hist[k * hist_stride] = |D x_{k+1}|_{2,1}, hist[k * hist_stride + hist_fid_offset] = |x_{k+1} - x0|^2
+ *                              (NOT halved: the two scalars tv_admm_tu and the last tv_cheb_step deliver) of the x outer iteration k formed.
+ *                              2 n_cheb phases per outer iteration; tv_small_workspace_bytes(g, n_outer) sizes `ws` for it as well, and one
+ *                              `ws` may serve the three loops in any order. */
 int    tv_small_supported(const tv_geom* g);
 size_t tv_small_workspace_bytes(const tv_geom* g, int64_t n_iter);
 int    tv_small_cp(const tv_geom* g, void* x, const void* x0, void* p, void* q, double sigma_D, double lambda, double tau,
                    double sigma_A, int64_t n_iter, double* hist, int64_t hist_stride, int64_t hist_fid_offset, void* ws, void* stream);
 int    tv_small_subgrad_descent(const tv_geom* g, void* x, void* x_alt, const void* x0, void* norms_ext, double step, double lambda,
                                 int64_t n_iter, double* hist, int64_t hist_stride, int64_t hist_fid_offset, void* ws, void* stream);
+int    tv_small_admm(const tv_geom* g, void* x, const void* x0, void* t, void* u, void* r, void* e_a, void* e_b, void* grad, double rho,
+                     double thresh, const double* alpha, const double* beta, int64_t n_cheb, int64_t n_outer, double* hist,
+                     int64_t hist_stride, int64_t hist_fid_offset, void* ws, void* stream);
 
 /* ---- multi-GPU: z-slab neighbours over RCCL, one process per GPU ------------------------------ */
 /* The reference is single-GPU (its README only remarks that the (Nz, M, N, N) layout "can be decomposed easily along z",

@@ -24,6 +24,10 @@
 //
 // Arithmetic per site is that of tv_cp_dual / tv_cp_primal / tv_subgrad + tv_subgrad_step (IEEE sqrt / divide): results equal the ordinary
 // small-volume path to rounding (the TV / fidelity sums group the sites differently).
+//
+// Round 7: k_small_admm runs the outer iterations of ADMM (Chebyshev x-solve) the same way -- generic form, the normal operator split into a
+// D phase and a D^T phase through a gradient scratch, 2 K phases per outer iteration; its phase list and the per-array argument for the
+// in-place updates stand in front of the kernel.
 #include <hip/hip_runtime.h>
 
 #include "tv_host.h"
@@ -1125,6 +1129,178 @@ __global__ __launch_bounds__(kSmallThreads) void k_small_sg(DG g, WT<T> w, Small
     }
 }
 
+// =================================================================================================================================
+// ADMM (round 7): n_outer outer iterations of scaled-form ADMM with K = n_cheb Chebyshev steps of the x-solve in ONE launch.  The scalars of
+// the Chebyshev iteration follow from the spectral interval alone, so an outer iteration needs neighbour data only -- what small_sync
+// synchronises.  Generic form (a loop over the virtual blocks of a range, as k_small_cp), per-site bodies d_site / dt_site / AdmmZU.
+//
+//   (I + rho D^T D) is applied in its SPLIT form: a D phase into a gradient scratch gs, a D^T phase out of it (radius 1 each; what
+//   small_dependency covers for every scheme).  The one-phase form from radius-2 reads was NOT built: tv_site.h has no per-site body for it
+//   and small_dependency has no radius-2 offsets inside a frame.
+//
+//   once per launch   P   : gs <- t - D x
+//   per outer iteration (2 K phases, one small_sync each):
+//     phase 0         B   : r <- (x0 - x) + rho D^T gs;  e_1 <- alpha_0 r                                  [K == 1: x <- x + e_1, |x - x0|^2]
+//     phase 2k-1      C_k : gs <- D e_k                                                                     k = 1 .. K-1
+//     phase 2k        D_k : e_{k+1} <- e_k + alpha_k (r - (e_k + rho D^T gs)) + beta_k (e_k - e_{k-1})      [k == K-1: x <- x + e_K, |x - x0|^2]
+//     phase 2K-1      Z   : v = D x + u; z = shrink(v, thresh); u <- v - z; t <- z - u; gs <- t - D x; |D x|_{2,1}
+//   The epoch advances by 1 + 2 K n_outer per call (the sync that would follow the last Z is not needed and not counted twice: the line
+//   behind the flags moves past every epoch a flag of this call holds).
+//
+//   Arrays and why each in-place overwrite is safe (a block passes the small_sync that closes phase X only when every block that owns a
+//   neighbouring site has FINISHED phase X, reads included; the relation is symmetric):
+//     x   CohMem.  Read at neighbours' sites in P / Z.  Written in B (K == 1) or D_{K-1}: at least one sync after the Z (or P) that read it.
+//     gs  CohMem.  Read at neighbours' sites in B and D_k.  Written in P, Z, C_k: each directly follows the sync that closed the B / D_k
+//         (or the previous launch) that read it.
+//     ea, eb  CohMem.  e_k lives in ea for odd k, eb for even k; read at neighbours' sites in C_k only.  D_k writes e_{k+1} over e_{k-1}:
+//         last read at a neighbour's site in C_{k-1}, two syncs earlier; B writes e_1 over the e_{K-1 or K-2} of the previous outer iteration.
+//     x0, r, t, u  ordinary accesses: touched at the own site only, always by the same thread.
+//   State on entry and exit: x, t = z - u, u (the arrays of the ordinary non-fused single-reduction path); r, ea, eb, gs are scratch.
+constexpr int kSmallMaxCheb = 32;
+
+template <typename T> struct SmallAdmmArgs {
+    T* x;
+    const T* x0;
+    T* t;
+    T* u;
+    T* r;
+    T* ea;
+    T* eb;
+    T* gs;
+    T rho, thresh;
+    int n_cheb;
+    T alpha[kSmallMaxCheb], beta[kSmallMaxCheb];
+    int n_iter;
+    unsigned* flags;
+    double* partials;        // [n_iter][2][nblocks]: |D x|_{2,1}, |x - x0|^2
+    long long x_bytes, q_bytes;
+};
+
+// gs <- D v, or t - D v (t != nullptr; t is read at the own site only)
+template <int S, typename T, int V> struct GradCoh {
+    static constexpr bool REDUCES = false;
+    T* gs;
+    const T* t;
+    CohMem mg;
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        const long long off = (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            constexpr int k = decltype(slot)::value;
+            const long long oc = off + (long long)ch * g.s_z;
+            mg.template st<T, V>(gs + oc, (t != nullptr) ? vload<T, V>(t + oc) - o[k] : o[k]);
+        });
+        return 0.0;
+    }
+};
+
+// the z / u update of tv_admm_tu (AdmmZU, tform) followed by gs <- t - D x of the site for the next right-hand side
+template <int S, typename T, int V> struct AdmmTuCoh {
+    static constexpr bool REDUCES = true;
+    AdmmZU<S, T, V> zu;
+    T* gs;
+    CohMem mg;
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        const double acc = zu(g, c, o);
+        const long long off = (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            constexpr int k = decltype(slot)::value;
+            const long long oc = off + (long long)ch * g.s_z;
+            mg.template st<T, V>(gs + oc, vload<T, V>(zu.z + oc) - o[k]);
+        });
+        return acc;
+    }
+};
+
+template <int S, typename T, int V>
+__global__ __launch_bounds__(kSmallThreads) void k_small_admm(DG g, WT<T> w, SmallPlan sp, SmallAdmmArgs<T> a) {
+    __shared__ double sm[16];
+    __shared__ int sh_abort;
+    if (threadIdx.x == 0) sh_abort = 0;
+    const int L = small_logical_id(sp);
+    if (L >= sp.nblocks) return;
+    const int dep = small_dependency(g, sp, L, (int)threadIdx.x);
+    unsigned epoch = small_epoch_base(a.flags);
+    const int vb0 = L * sp.per_block, vb1 = (vb0 + sp.per_block < sp.nvb) ? vb0 + sp.per_block : sp.nvb;
+    const int K = a.n_cheb;
+    const CohMem mx = CohMem::make(a.x, a.x_bytes), mg = CohMem::make(a.gs, a.q_bytes);
+    const CohMem mea = CohMem::make(a.ea, a.x_bytes), meb = CohMem::make(a.eb, a.x_bytes);
+    const SrcCoh<T, V> src{a.gs, mg};
+    const AdmmTuCoh<S, T, V> tu{AdmmZU<S, T, V>{a.t, a.u, a.thresh, nullptr, 1}, a.gs, mg};
+
+    // a D phase: gs <- [t -] D v over my sites
+    auto grad = [&](const T* v, const CohMem& mv, const T* t) {
+        const GradCoh<S, T, V> epi{a.gs, t, mg};
+        for (int vb = vb0; vb < vb1; ++vb) {
+            const Coord c = small_coord<V>(g, sp, vb);
+            d_site<S, T, V>(g, w, v, (const T*)nullptr, (const T*)nullptr, 1, c, epi, mv);
+        }
+    };
+    // a D^T phase: step k of the x-solve (k == 0 forms r first); returns |x - x0|^2 of my sites when it forms the new x
+    auto solve_step = [&](int k) -> double {
+        const bool first = (k == 0), last = (k + 1 == K);
+        const T al = a.alpha[k], be = a.beta[k];
+        T* ek = (k & 1) ? a.ea : a.eb;            // e_k (k >= 1)
+        T* en = (k & 1) ? a.eb : a.ea;            // e_{k+1}, over e_{k-1}
+        const CohMem& mk = (k & 1) ? mea : meb;
+        const CohMem& mn = (k & 1) ? meb : mea;
+        double acc = 0.0;
+        for (int vb = vb0; vb < vb1; ++vb) {
+            const Coord c = small_coord<V>(g, sp, vb);
+            if (c.ok) {
+                long long inpl;
+                const Vec<T, V> dt = dt_site<S, T, V>(g, w, src, c, inpl);
+                const long long off = (long long)c.zl * g.s_z + inpl;
+                Vec<T, V> e;
+                if (first) {
+                    const Vec<T, V> rv = (vload<T, V>(a.x0 + off) - mx.template ld<T, V>(a.x + off)) + a.rho * dt;
+                    if (!last) vstore<T, V>(a.r + off, rv);
+                    e = al * rv;
+                } else {
+                    const Vec<T, V> ev = mk.template ld<T, V>(ek + off), rv = vload<T, V>(a.r + off);
+                    const Vec<T, V> ep = (k >= 2) ? mn.template ld<T, V>(en + off) : vsplat<T, V>(T(0));
+                    e = (ev + al * (rv - (ev + a.rho * dt))) + be * (ev - ep);
+                }
+                if (last) {
+                    const Vec<T, V> xn = mx.template ld<T, V>(a.x + off) + e, x0v = vload<T, V>(a.x0 + off);
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        const double df = (double)xn.v[i] - (double)x0v.v[i];
+                        acc += df * df;
+                    }
+                    mx.template st<T, V>(a.x + off, xn);
+                } else {
+                    mn.template st<T, V>(en + off, e);
+                }
+            }
+        }
+        return acc;
+    };
+
+    grad(a.x, mx, a.t);                                                                    // P
+    if (small_sync(a.flags, L, dep, ++epoch, &sh_abort)) return;
+    for (int it = 0; it < a.n_iter; ++it) {
+        double fid = 0.0;
+        for (int k = 0; k < K; ++k) {
+            if (k > 0) {
+                grad((k & 1) ? a.ea : a.eb, (k & 1) ? mea : meb, (const T*)nullptr);       // C_k
+                if (small_sync(a.flags, L, dep, ++epoch, &sh_abort)) return;
+            }
+            fid = solve_step(k);                                                           // B / D_k
+            if (small_sync(a.flags, L, dep, ++epoch, &sh_abort)) return;
+        }
+        fid = block_sum(fid, sm);
+        if (threadIdx.x == 0) a.partials[((long long)it * 2 + 1) * sp.nblocks + L] = fid;
+        double acc = 0.0;                                                                  // Z
+        for (int vb = vb0; vb < vb1; ++vb) {
+            const Coord c = small_coord<V>(g, sp, vb);
+            acc += d_site<S, T, V>(g, w, (const T*)a.x, (const T*)nullptr, (const T*)nullptr, 1, c, tu, mx);
+        }
+        acc = block_sum(acc, sm);
+        if (threadIdx.x == 0) a.partials[((long long)it * 2 + 0) * sp.nblocks + L] = acc;
+        if (it + 1 < a.n_iter && small_sync(a.flags, L, dep, ++epoch, &sh_abort)) return;
+    }
+}
+
 // hist[(row / 2) * stride + (row & 1 ? fid_offset : 0)] = sum over the blocks of partials[row][*] (fixed order: deterministic); the first
 // block also advances the workspace's epoch past this call's phases
 __global__ __launch_bounds__(256) void k_small_reduce(const double* partials, int nblocks, double* hist, long long stride, long long fid_offset,
@@ -1235,14 +1411,15 @@ static size_t small_flag_bytes() { return (size_t)(kMaxSmallBlocks + 1) * kFlagS
 // one call of a persistent loop: pick the form, split the workspace, launch cooperatively, reduce the partials into hist
 template <typename T, typename Args>
 static int small_launch(const DG& d, int V, WT<T> w, Args a, const void* reg_kern, const void* flat_kern, const void* generic_kern, double* hist,
-                        int64_t hist_stride, int64_t hist_fid_offset, void* ws, hipStream_t st, const char* who) {
+                        int64_t hist_stride, int64_t hist_fid_offset, void* ws, hipStream_t st, const char* who, unsigned advance = 0) {
+    // reg_kern / flat_kern == nullptr: the loop has the generic form only; advance: phases the call adds to the epoch (0: two per iteration)
     const void* kern = reg_kern;
     SmallPlan sp;
     int threads = kSmallThreads;
     // TV_SMALL_SITES: 0 = resident form first, then the streamed form with 2 .. 4 site-vectors per thread; 1 = resident only; 2 .. 4 = streamed from there
     const int s0 = env_int("TV_SMALL_SITES", 0);
-    bool flat = s0 <= 1 && small_plan_flat(d, V, kern, sp, threads);
-    for (int sites = s0 > 2 ? s0 : 2; !flat && sites <= kFlatMaxSites && s0 != 1; ++sites) {
+    bool flat = reg_kern != nullptr && s0 <= 1 && small_plan_flat(d, V, kern, sp, threads);
+    for (int sites = s0 > 2 ? s0 : 2; flat_kern != nullptr && !flat && sites <= kFlatMaxSites && s0 != 1; ++sites) {
         kern = flat_kern;
         flat = small_plan_flat(d, V, kern, sp, threads, sites);
     }
@@ -1260,7 +1437,7 @@ static int small_launch(const DG& d, int V, WT<T> w, Args a, const void* reg_ker
     void* args[] = {&dd, &w, &sp, &a};
     HIP_TRY(hipLaunchCooperativeKernel(kern, dim3((unsigned)sp.grid), dim3((unsigned)threads), args, 0, st));
     hipLaunchKernelGGL(k_small_reduce, dim3((unsigned)(2 * a.n_iter)), dim3(256), 0, st, (const double*)a.partials, sp.nblocks, hist, (long long)hist_stride,
-                       (long long)hist_fid_offset, a.flags, (unsigned)(2 * a.n_iter));
+                       (long long)hist_fid_offset, a.flags, advance ? advance : (unsigned)(2 * a.n_iter));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1323,6 +1500,37 @@ int tv_small_subgrad_descent(const tv_geom* g, void* x, void* x_alt, const void*
                          d.s_z * d.nz * (long long)sizeof(T), d.s_z * (d.nz + 2) * (long long)sizeof(T)};
         return small_launch(d, V, make_w<T>(g), a, (const void*)k_small_sg_reg<S, T, V>, (const void*)k_small_sg_flat<S, T, V>, (const void*)k_small_sg<S, T, V>,
                             hist, hist_stride, hist_fid_offset, ws, (hipStream_t)stream, "tv_small_subgrad_descent");
+    });
+}
+
+int tv_small_admm(const tv_geom* g, void* x, const void* x0, void* t, void* u, void* r, void* e_a, void* e_b, void* grad, double rho, double thresh,
+                  const double* alpha, const double* beta, int64_t n_cheb, int64_t n_outer, double* hist, int64_t hist_stride, int64_t hist_fid_offset,
+                  void* ws, void* stream) {
+    DG d;
+    if (int rc = small_check(g, d, "tv_small_admm")) return rc;
+    if (x == nullptr || x0 == nullptr || t == nullptr || u == nullptr || r == nullptr || e_a == nullptr || e_b == nullptr || grad == nullptr ||
+        alpha == nullptr || beta == nullptr || hist == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
+    const void* arrs[] = {x, x0, t, u, r, e_a, e_b, grad};
+    for (int i = 0; i < 8; ++i)
+        for (int j = i + 1; j < 8; ++j)
+            if (arrs[i] == arrs[j]) return fail(TV_E_ARG, "tv_small_admm: x, x0, t, u and the scratch arrays r, e_a, e_b, grad must be different arrays");
+    if (!(rho > 0.0)) return fail(TV_E_ARG, "rho must be > 0");
+    if (!(thresh >= 0.0)) return fail(TV_E_ARG, "thresh must be >= 0");
+    if (n_cheb < 1 || n_cheb > kSmallMaxCheb) return fail(TV_E_ARG, "n_cheb out of range (1 .. 32 Chebyshev steps per outer iteration)");
+    if (n_outer < 1 || n_outer > (1 << 20) / (2 * n_cheb)) return fail(TV_E_ARG, "n_outer out of range");
+    if (hist_stride < 1 || hist_fid_offset == 0 || hist_fid_offset >= hist_stride || hist_fid_offset < 0) return fail(TV_E_ARG, "hist_stride / hist_fid_offset: 0 < fid_offset < stride");
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x0, t, u, r, e_a, e_b, grad, d.wv});
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        SmallAdmmArgs<T> a{};
+        a.x = (T*)x; a.x0 = (const T*)x0; a.t = (T*)t; a.u = (T*)u; a.r = (T*)r; a.ea = (T*)e_a; a.eb = (T*)e_b; a.gs = (T*)grad;
+        a.rho = (T)rho; a.thresh = (T)thresh;
+        a.n_cheb = (int)n_cheb;
+        for (int k = 0; k < (int)n_cheb; ++k) { a.alpha[k] = (T)alpha[k]; a.beta[k] = (T)beta[k]; }
+        a.n_iter = (int)n_outer;
+        a.x_bytes = d.s_z * d.nz * (long long)sizeof(T);
+        a.q_bytes = d.s_dz * d.nz * (long long)sizeof(T);
+        return small_launch(d, V, make_w<T>(g), a, nullptr, nullptr, (const void*)k_small_admm<S, T, V>, hist, hist_stride, hist_fid_offset, ws,
+                            (hipStream_t)stream, "tv_small_admm", (unsigned)(1 + 2 * n_cheb * n_outer));
     });
 }
 

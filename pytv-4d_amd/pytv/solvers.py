@@ -1287,8 +1287,13 @@ class ADMM(_SlabProblem):
 
     def __init__(self, x0, regularization, rho, n_cg=10, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0,
                  mask_static=False, factor_reg_static=0, slab=None, single_reduction=True, fused=None, keep_z=True, x_solver=None,
-                 pitch="auto", tune_placement=None):
-        """tune_placement: None = on for unsharded problems whose state is >= 16 GiB with room for a second copy (``_tune_placement``)."""
+                 pitch="auto", tune_placement=None, persistent=False):
+        """tune_placement: None = on for unsharded problems whose state is >= 16 GiB with room for a second copy (``_tune_placement``).
+        persistent (round 7): True = ``run`` goes through ``SMALL_BLOCK`` outer iterations per cooperative launch (tv_small_admm: the
+        Chebyshev x-solve and the z / u update inside a persistent kernel, csrc/tv_small.hip) -- for unsharded volumes tv_small_supported
+        accepts, single_reduction, the Chebyshev x-solve, n_cg in 1 .. 32; it selects the non-fused state convention (x, t = z - u, u), so
+        ``step`` / ``.x`` / ``.u`` / ``.z`` / ``result()`` work as on the ordinary non-fused path and can be mixed with ``run``.
+        False (the default) = the ordinary kernels; there is no automatic rule."""
         super().__init__(x0, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch=pitch)
         self.reg, self.rho, self.n_cg = float(regularization), float(rho), int(n_cg)
         self.single = bool(single_reduction)
@@ -1303,6 +1308,7 @@ class ADMM(_SlabProblem):
         # objective to 6 - 7 digits at EVERY outer iteration, and a Chebyshev outer iteration takes 12.8 - 16.3 ms where CG takes
         # 27 - 33 (fp64: 15 - 21 against 29 - 37): 2.1 - 2.4 x less wall time to any objective level, no all-reduce in the solve.
         # ``n_cg`` keeps its meaning: steps of the x-solve per outer iteration.  x_solver="cg" is the round-1..3 behaviour.
+        x_solver_asked = x_solver
         if x_solver is None:
             x_solver = "chebyshev" if (self.single and self.n_cg > 0) else "cg"
         if x_solver not in ("cg", "chebyshev"):
@@ -1323,6 +1329,18 @@ class ADMM(_SlabProblem):
         if fused and not can_fuse:
             raise ValueError("fused=True needs single_reduction, n_cg > 0 and a geometry tv_cp_fused_supported() accepts")
         self.fused = can_fuse if fused is None else bool(fused)
+        self.small = False
+        if persistent:
+            if x_solver_asked == "cg" or not self.cheb:
+                raise ValueError("persistent=True runs the Chebyshev x-solve (x_solver=None or 'chebyshev', single_reduction=True, n_cg >= 1): "
+                                 "CG needs a grid-wide dot product per step")
+            if fused:
+                raise ValueError("persistent=True keeps the non-fused state convention (x, t, u): fused=True cannot be combined with it")
+            if self.n_cg > self.SMALL_MAX_CHEB:
+                raise ValueError("persistent=True: at most %d Chebyshev steps per outer iteration (n_cg)" % self.SMALL_MAX_CHEB)
+            self.small = self._small_ok(True)       # raises for a sharded slab / a volume outside tv_small_supported
+            self.fused = False
+        self._small_grad = None
         self.keep_z = bool(keep_z)
         self._have_r = False
         self.x = self.image_copy(self.x0)
@@ -1722,12 +1740,44 @@ class ADMM(_SlabProblem):
 
     GRAPH_BLOCK = 4             # outer iterations captured per hipGraph
     GRAPH_MAX_VOXELS = 1 << 23  # below this an outer iteration (~10 + 2 n_cg launches) is launch-bound
+    SMALL_MAX_CHEB = 32         # Chebyshev steps per outer iteration the persistent kernel takes (csrc/tv_small.hip: kSmallMaxCheb)
+
+    def _small_now(self):
+        """the persistent path runs the loop unless somebody asked for per-step events (``timing``)"""
+        return self.small and self.timing is None
+
+    def _run_small(self, rows):
+        """``len(rows)`` outer iterations in blocks of ``SMALL_BLOCK`` per cooperative launch (tv_small_admm): x, t, u updated in place;
+        |D x|_{2,1} -> slot 0, |x - x0|^2 -> slot 1 of every row (the slots ``step`` fills).  r, d, Ad and a gradient array are scratch."""
+        import ctypes
+        ws = self._small_ws()
+        if self._small_grad is None:
+            self._small_grad = self.new_grad()
+        K = self.n_cg
+        alpha = (ctypes.c_double * K)(*[c[0] for c in self._cheb_coef])
+        beta = (ctypes.c_double * K)(*[c[1] for c in self._cheb_coef])
+        n, done = rows.shape[0], 0
+        if rows.stride(1) != 1:
+            raise ValueError("rows must be a (n, 2) fp64 tensor with contiguous rows")
+        while done < n:
+            k = min(self.SMALL_BLOCK, n - done)
+            _nv.check(self.lib.tv_small_admm(self.geo.ref, _nv.ptr(self.x), _nv.ptr(self.x0), _nv.ptr(self._zt), _nv.ptr(self.u), _nv.ptr(self.r),
+                                             _nv.ptr(self.d), _nv.ptr(self.Ad), _nv.ptr(self._small_grad), self.rho, self.reg / self.rho, alpha, beta,
+                                             K, k, rows[done].data_ptr(), rows.stride(0), 1, _nv.ptr(ws), self.stream))
+            done += k
 
     def run(self, n_outer, graph=None):
         """n_outer outer iterations; returns the loss history.  graph: None = replay blocks of GRAPH_BLOCK outer iterations
         from a hipGraph when the problem is small enough to be launch-bound and not sharded (every scalar of the CG recurrence
-        lives on the device, so an outer iteration has no host round trip to break the capture); True / False force it."""
+        lives on the device, so an outer iteration has no host round trip to break the capture); True / False force it.
+        ``persistent=True`` (and no ``timing``): the persistent kernel IS the loop, ``graph`` is not consulted."""
         hist = torch.zeros((n_outer, 2), dtype=torch.float64, device=self.device)
+        if self._small_now():
+            if n_outer > 0:
+                self._run_small(hist)
+            self._small_check()
+            h = hist.cpu().numpy()
+            return 0.5 * h[:, 1] + self.reg * h[:, 0]
         use_graph = (self.x0.numel() <= self.GRAPH_MAX_VOXELS) if graph is None else bool(graph)
         start = 0
         if use_graph and not self.slab.sharded and n_outer >= 2 + 2 * self.GRAPH_BLOCK:

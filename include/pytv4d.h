@@ -195,7 +195,12 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
  * Both can be restricted to a range so that halo exchanges hide behind the interior work: the sweep to
  * z-chunks [chunk_begin, chunk_begin + chunk_count) (tv_cp_zchunk() planes each, chunk_count < 0 = all),
  * the fix-up to local planes [z_begin, z_begin + z_count) (z_count < 0 = all).  Only the first chunk reads
- * x_prev, only the last x_next; only plane 0 reads q_prev, only plane nz-1 q_next.                         */
+ * x_prev, only the last x_next; only plane 0 reads q_prev, only plane nz-1 q_next.
+ * Ranges are exact: whichever way the chunks and planes are split over calls, every array comes out bit-identical to the whole
+ * call, and the partial *tv / *fid add up to its scalars (to the last digits of an fp64 sum).  Seams are not: x_out (r of the ADMM
+ * form) of a site next to a chunk or slab seam is rounded once by the sweep and once more by the fix-up, a site inside a chunk once
+ * only -- slabs reproduce the unsharded x_out bit for bit when their cuts are multiples of the unsharded tv_cp_zchunk(), and to
+ * the rounding of the dtype otherwise; q, u and every stored sample of t' never depend on the seams (tests/test_gpu_sweep_ranges.py). */
 int tv_cp_fused_supported(const tv_geom* g);
 int tv_cp_zchunk(const tv_geom* g);
 int tv_cp_fused(const tv_geom* g, const void* x_in, const void* x_prev, const void* x_next, void* q, const void* x0,

@@ -87,6 +87,11 @@ def auto_pitch(ny, nx, dtype, frame_pad_bytes=0):
     return rp, ny * rp + pad
 
 
+def _plane0(halo):
+    """plane 0 of an optional halo buffer"""
+    return halo[0] if halo is not None else None
+
+
 class _SlabProblem:
     """Common state: local slab geometry (and sub-slab geometries for interior / edge launches)."""
 
@@ -165,6 +170,17 @@ class _SlabProblem:
             nbytes = self.lib.tv_small_workspace_bytes(self.geo.ref, self.SMALL_BLOCK)
             self._small_ws_buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
         return self._small_ws_buf
+
+    def _small_blocks(self, rows, launch):
+        """``len(rows)`` iterations in blocks of ``SMALL_BLOCK`` per cooperative launch: ``launch(k, row_ptr)`` enqueues k of them, the reduction
+        that closes the launch writing their scalars into the rows from ``row_ptr`` on (stride ``rows.stride(0)``)."""
+        if rows.stride(1) != 1:
+            raise ValueError("rows must be a (n, %d) fp64 tensor with contiguous rows" % rows.shape[1])
+        n, done = rows.shape[0], 0
+        while done < n:
+            k = min(self.SMALL_BLOCK, n - done)
+            launch(k, rows[done].data_ptr())
+            done += k
 
     # 32-bit word of the workspace that a launch raises when it abandons itself (csrc/tv_small.hip: small_abort_word, kMaxSmallBlocks * kFlagStride + 1)
     SMALL_ABORT_WORD = 8192 * 32 + 1
@@ -295,6 +311,129 @@ class _SlabProblem:
         out.copy_(src)
         return out
 
+    def result(self):
+        """The iterate as a DENSE (Nz, M, Ny, Nx) tensor: with padded state (``pitch``) a contiguous copy -- callers that ``.view(-1)``
+        it, take its ``data_ptr()`` or hand it to the dense ``tv_*`` entry points must not see pad columns (round-4 advice); ``.x``
+        stays the raw (possibly strided) view of the solver's storage."""
+        return self.x.contiguous() if self.pitch != (0, 0) else self.x
+
+    # ---- hipGraph replay of the loop -------------------------------------------------------------------------------------------------
+    _ROLES = ()     # the attributes whose bindings a step() may rotate at Python level (buffer ping-pongs, counters)
+
+    def _run_graphed_head(self, hist, use_graph):
+        """Two eager iterations (also the warm-up of the capture), then graph replays over the rows of ``hist``; returns the row at which
+        the caller's eager tail starts (0: nothing ran)."""
+        n = hist.shape[0]
+        if not (use_graph and not self.slab.sharded and n >= 2 + 2 * self.GRAPH_BLOCK):
+            return 0
+        self.step(hist[0])
+        self.step(hist[1])
+        return 2 + self._run_graphed_from(hist, 2, n)
+
+    def _run_graphed_from(self, hist, first, n_iter):
+        """Capture GRAPH_BLOCK iterations (not executed during capture) and replay them over hist[first:]; returns how many iterations ran."""
+        K = self.GRAPH_BLOCK
+        nrep = (n_iter - first) // K
+        if nrep < 1:
+            return 0
+        # the steps REBIND buffers at Python level (x / x_alt, q / q_alt, u / u_alt; the Chebyshev x-solve writes the new image next to
+        # the old one and swaps x / d / Ad / b): a capture that fails part-way must not leave them pointing at buffers whose kernels
+        # never ran (round-3 advice)
+        saved = {k: getattr(self, k) for k in self._ROLES if hasattr(self, k)}
+        try:
+            buf = torch.zeros((K, hist.shape[1]), dtype=torch.float64, device=self.device)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for k in range(K):
+                    self.step(buf[k])
+            # a block that does not return the buffers to their roles (odd number of role swaps) would not be the same iteration when
+            # it is replayed -- cannot happen with GRAPH_BLOCK even, checked all the same
+            ok = all(getattr(self, k) is v for k, v in saved.items() if isinstance(v, torch.Tensor))
+        except Exception:
+            ok = False
+        for k, v in saved.items():               # nothing ran: undo the bookkeeping (the counters too)
+            setattr(self, k, v)
+        if not ok:
+            return 0                             # stay eager
+        done = 0
+        for r in range(nrep):
+            graph.replay()
+            hist[first + done:first + done + K].copy_(buf)
+            done += K
+        return done
+
+    # ---- placement of an x -> x_alt ping-pong by measurement (ChambollePock._tune_x_placement, SubgradientDescent._tune_placement) ------
+    # ``launch()`` enqueues one x -> x_alt step of the solver's real kernel with whatever is bound NOW (x, x_alt, x0, p, q).
+    def _pp_one(self, launch, i_buf, o_buf):
+        """one timed step i_buf -> o_buf; returns its event pair"""
+        self.x, self.x_alt = i_buf, o_buf
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        launch()
+        b.record()
+        return a, b
+
+    def _pp_round_trip(self, launch, u, v, reps, skip=0):
+        """ms of u -> v plus v -> u (best of ``reps``, after ``skip`` repetitions that are not counted); leaves x = u, x_alt = v bound"""
+        evs = [(self._pp_one(launch, u, v), self._pp_one(launch, v, u)) for _ in range(skip + reps)][skip:]
+        torch.cuda.synchronize(self.device)
+        self.x, self.x_alt = u, v
+        return min(e[0][0].elapsed_time(e[0][1]) for e in evs) + min(e[1][0].elapsed_time(e[1][1]) for e in evs)
+
+    def _pp_pairs(self, launch, cands, reps):
+        """Every ordered pair of the candidates timed (best of ``reps``): (ms[i][j] of i -> j rounded, None on the diagonal; the best unordered
+        pair [i, j]; its two directions in ms; those of the first pair)."""
+        n = len(cands)
+        ev = [[[] for _ in range(n)] for _ in range(n)]
+        for r in range(reps):
+            for i in range(n):
+                for j in range(n):
+                    if i != j:
+                        ev[i][j].append(self._pp_one(launch, cands[i], cands[j]))
+        torch.cuda.synchronize(self.device)
+        t = [[(min(a.elapsed_time(b) for a, b in ev[i][j]) if i != j else float("inf")) for j in range(n)] for i in range(n)]
+        _, bi, bj = min(((t[i][j] + t[j][i], i, j) for i in range(n) for j in range(i + 1, n)))
+        return ([[None if i == j else round(t[i][j], 3) for j in range(n)] for i in range(n)], [bi, bj],
+                [round(t[bi][bj], 3), round(t[bj][bi], 3)], [round(t[0][1], 3), round(t[1][0], 3)])
+
+    def _pp_x0(self, launch, u, v, spare, reps):
+        """x0 (read once per step): the caller's array against a copy in ``spare``, a buffer that is left; returns the two round trips in ms
+        and keeps the copy only if it is strictly faster."""
+        x0_orig = self.x0
+        spare.copy_(x0_orig)
+        t0 = self._pp_round_trip(launch, u, v, reps)
+        self.x0 = spare
+        t1 = self._pp_round_trip(launch, u, v, reps)
+        if t0 <= t1:
+            self.x0 = x0_orig
+        return [round(t0, 3), round(t1, 3)]
+
+    def _reset_state(self):
+        """Back to the state of a fresh solver in the arrays that are bound now."""
+        self.x.copy_(self.x0)
+
+    def _pp_tune(self, tune_placement, allowed, keep, tune):
+        """Constructor side of the tuners.  tune_placement None = the automatic rule: images of >= 4 GiB with room for three more and 8 GiB to
+        spare, where the solver allows it (``allowed``).  Sharded slabs too: the tuner launches local kernels only, no rank waits for another;
+        every rank of a weak-scaling run holds a slab of the single-GPU size and plays the same placement lottery.
+        The tuner is an optimisation, never a failure (out of memory while holding the candidates, ...): the bindings named in ``keep`` are
+        put back and the state is re-initialised."""
+        if tune_placement is None:
+            img_bytes = self.x.numel() * self.x.element_size()
+            free, _total = torch.cuda.mem_get_info(self.device)
+            tune_placement = allowed and img_bytes >= (4 << 30) and free >= 3 * img_bytes + (8 << 30)
+        if not tune_placement:
+            return
+        kept = [(k, getattr(self, k)) for k in keep]
+        try:
+            tune()
+        except RuntimeError as exc:
+            for k, v in kept:
+                setattr(self, k, v)
+            self._reset_state()
+            torch.cuda.empty_cache()
+            self.placement = {"error": str(exc)[:200]}
+
 
 # =================================================================================================
 class ChambollePock(_SlabProblem):
@@ -395,27 +534,18 @@ class ChambollePock(_SlabProblem):
             if img_bytes >= (4 << 30) and free >= self._arena.numel() * self._arena.element_size() + (8 << 30):
                 self._tune_arena()
         if self.fused:
-            img_bytes = self.x.numel() * self.x.element_size()
-            if tune_placement is None:
-                free, _total = torch.cuda.mem_get_info(self.device)
-                # (sharded slabs too: the tuner launches local kernels only, no rank waits for another; every rank of a weak-scaling run
-                # holds a slab of the single-GPU size and plays the same placement lottery)
-                tune_placement = (not self.arena) and img_bytes >= (4 << 30) and free >= 3 * img_bytes + (8 << 30)
-            if tune_placement:
-                # (q is NOT pinned here: the tuner keeps exactly one q bound at any time -- the best so far -- and at most one
-                # candidate beside it, so that a winning candidate frees the original before the next one is allocated; round-4 advice)
-                keep = (self.x, self.x_alt, self.p, self.x0)
-                try:
-                    self._tune_x_placement()
-                except RuntimeError as exc:       # out of memory while holding the candidates, ...: the tuner is an optimisation, never a failure
-                    self.x, self.x_alt, self.p, self.x0 = keep
-                    self._lag = None
-                    self.x.copy_(self.x0)
-                    self.p.zero_()
-                    self.q.zero_()
-                    torch.cuda.empty_cache()
-                    self.placement = {"error": str(exc)[:200]}
-                del keep
+            # (q is NOT kept: the tuner keeps exactly one q bound at any time -- the best so far -- and at most one
+            # candidate beside it, so that a winning candidate frees the original before the next one is allocated; round-4 advice)
+            self._pp_tune(tune_placement, not self.arena, ("x", "x_alt", "p", "x0"), self._tune_x_placement)
+
+    def _reset_state(self):
+        """Back to the initial state: x = x0, p = q = q_alt = 0, no lagged-fidelity block open."""
+        self._lag = None
+        self.x.copy_(self.x0)
+        self.p.zero_()
+        self.q.zero_()
+        if self.q_alt is not None:
+            self.q_alt.zero_()
 
     def _alloc_state(self):
         """(Re)allocate x, x_alt, p, the private copy of x0, q [, q_alt] -- out of a fresh arena when one can be had -- and put them
@@ -444,21 +574,10 @@ class ChambollePock(_SlabProblem):
         t_begin = _time.perf_counter()
         out = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
 
-        def round_trip():
+        def round_trip():                        # the first of reps + 1 repetitions is the warm-up
             hp = self.x[0:1] if self.plan.x_need_prev else None
             hn = self.x[0:1] if self.plan.x_need_next else None
-            ts = []
-            for r in range(reps + 1):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                self._sweep(0, -1, hp, hn, out[0:1], out[self.F:self.F + 1])
-                self.x, self.x_alt = self.x_alt, self.x
-                self._sweep(0, -1, hp, hn, out[0:1], out[self.F:self.F + 1])
-                self.x, self.x_alt = self.x_alt, self.x
-                b.record()
-                ts.append((a, b))
-            torch.cuda.synchronize(self.device)
-            return min(a.elapsed_time(b) for a, b in ts[1:])
+            return self._pp_round_trip(lambda: self._sweep(0, -1, hp, hn, out[0:1], out[self.F:self.F + 1]), self.x, self.x_alt, reps, skip=1)
 
         names = ("_arena", "_arena_off", "_arena_gap", "x", "x_alt", "p", "x0", "q", "q_alt")
         t0 = round_trip()
@@ -480,11 +599,7 @@ class ChambollePock(_SlabProblem):
             info["error"] = str(exc)[:160]
         del first
         torch.cuda.empty_cache()
-        self.x.copy_(self.x0)
-        self.p.zero_()
-        self.q.zero_()
-        if self.q_alt is not None:
-            self.q_alt.zero_()
+        self._reset_state()
         torch.cuda.synchronize(self.device)
         info["chosen"] = int(len(info["round_trip_ms"]) == 2 and info["round_trip_ms"][1] < info["round_trip_ms"][0])
         info["seconds"] = round(_time.perf_counter() - t_begin, 3)
@@ -524,23 +639,15 @@ class ChambollePock(_SlabProblem):
         hn = self.x[0:1] if self.plan.x_need_next else None
         info = {}
 
-        def one(i_buf, o_buf):
-            self.x, self.x_alt = i_buf, o_buf
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
+        def launch():
             self._sweep(0, -1, hp, hn, out[0:1], out[self.F:self.F + 1])
-            b.record()
-            return a, b
 
         def round_trip(u, v):
-            """ms of u -> v plus v -> u (best of ``reps``)"""
-            evs = [(one(u, v), one(v, u)) for _ in range(reps)]
-            torch.cuda.synchronize(self.device)
-            return min(e[0][0].elapsed_time(e[0][1]) for e in evs) + min(e[1][0].elapsed_time(e[1][1]) for e in evs)
+            return self._pp_round_trip(launch, u, v, reps)
 
         x_a, x_b = self.x, self.x_alt
         for _ in range(2):                                                   # warm-up (code load, clocks)
-            one(x_a, x_b)
+            self._pp_one(launch, x_a, x_b)
         # ---- the dual variable: one alternative allocation, if it fits with room to spare ---------------------------------------
         q_bytes = self.q.numel() * self.q.element_size()
         img_bytes = x_a.numel() * x_a.element_size()
@@ -568,19 +675,8 @@ class ChambollePock(_SlabProblem):
             del best_q
         # ---- the image pair: every ordered pair of the candidates ------------------------------------------------------------------
         cands = [x_a, x_b] + [self.new_image() for _ in range(n_extra)]
-        n = len(cands)
-        ev = [[[] for _ in range(n)] for _ in range(n)]
-        for r in range(reps):
-            for i in range(n):
-                for j in range(n):
-                    if i != j:
-                        ev[i][j].append(one(cands[i], cands[j]))
-        torch.cuda.synchronize(self.device)
-        t = [[(min(a.elapsed_time(b) for a, b in ev[i][j]) if i != j else float("inf")) for j in range(n)] for i in range(n)]
-        _, bi, bj = min(((t[i][j] + t[j][i], i, j) for i in range(n) for j in range(i + 1, n)))
-        info.update({"candidates": n, "sweep_ms": [[None if i == j else round(t[i][j], 3) for j in range(n)] for i in range(n)],
-                     "chosen": [bi, bj], "chosen_ms": [round(t[bi][bj], 3), round(t[bj][bi], 3)],
-                     "first_pair_ms": [round(t[0][1], 3), round(t[1][0], 3)]})
+        ms, (bi, bj), chosen_ms, first_ms = self._pp_pairs(launch, cands, reps)
+        info.update({"candidates": len(cands), "sweep_ms": ms, "chosen": [bi, bj], "chosen_ms": chosen_ms, "first_pair_ms": first_ms})
         x_a, x_b = cands[bi], cands[bj]
         # ---- the fidelity dual p: the candidates that are left, against the allocation it has ------------------------------------------
         rest = [c for k, c in enumerate(cands) if k not in (bi, bj)]
@@ -598,23 +694,10 @@ class ChambollePock(_SlabProblem):
         spare = [c for k, c in enumerate(p_cands) if k != kp]
         del p_cands, rest
         if spare:
-            x0_orig, x0_copy = self.x0, spare[0]
-            x0_copy.copy_(x0_orig)
-            t0_ = round_trip(x_a, x_b)
-            self.x0 = x0_copy
-            t1_ = round_trip(x_a, x_b)
-            info["x0_round_trip_ms"] = [round(t0_, 3), round(t1_, 3)]
-            if t0_ <= t1_:
-                self.x0 = x0_orig
-            del x0_orig, x0_copy
+            info["x0_round_trip_ms"] = self._pp_x0(launch, x_a, x_b, spare[0], reps)
         del spare
         self.x, self.x_alt = x_a, x_b
-        # back to the initial state: x = x0, p = q = 0 (the timed sweeps wrote into them)
-        self.x.copy_(self.x0)
-        self.p.zero_()
-        self.q.zero_()
-        if self.q_alt is not None:
-            self.q_alt.zero_()
+        self._reset_state()                          # the timed sweeps wrote into x, p and q
         torch.cuda.synchronize(self.device)
         torch.cuda.empty_cache()
         info["seconds"] = round(_time.perf_counter() - t_begin, 3)
@@ -665,8 +748,7 @@ class ChambollePock(_SlabProblem):
         self._cur_out = out
         ev = self._events()
         mark = self._phase_marker()
-        qhp = self.qh_prev[0] if self.qh_prev is not None else None
-        qhn = self.qh_next[0] if self.qh_next is not None else None
+        qhp, qhn = _plane0(self.qh_prev), _plane0(self.qh_next)
         mark("start")
         h = self.plan.exchange_image(self.x, self.xh_prev, self.xh_next)
         if ev:
@@ -781,8 +863,7 @@ class ChambollePock(_SlabProblem):
         if ev:
             ev[1].record()
         # ---------------- primal: x <- x - tau p - tau D^T q ---------------------------------------
-        h = self.plan.exchange_grad(q, self.qh_prev[0] if self.qh_prev is not None else None,
-                                    self.qh_next[0] if self.qh_next is not None else None)
+        h = self.plan.exchange_grad(q, _plane0(self.qh_prev), _plane0(self.qh_next))
         if self.overlap:
             self._primal(1, nz - 1, q[0, self.ch_back], q[nz - 1, self.ch_fwd], out[F:F + 1])
             mark("primal_interior")
@@ -812,13 +893,7 @@ class ChambollePock(_SlabProblem):
         small = self._small_now()
         if small and graph is None:
             use_graph = False                     # the persistent kernel IS the loop: nothing left to capture
-        start = 0
-        if use_graph and n_iter >= 2 + 2 * self.GRAPH_BLOCK and not self.slab.sharded:
-            # two eager iterations (also the warm-up of the capture), then graph replays, then an eager tail
-            self.step(hist[0])
-            self.step(hist[1])
-            done = self._run_graphed_from(hist, 2, n_iter)
-            start = 2 + max(done, 0)
+        start = self._run_graphed_head(hist, use_graph)
         self.run_steps(hist[start:n_iter])
         if small:
             self._small_check()
@@ -859,47 +934,21 @@ class ChambollePock(_SlabProblem):
         """``len(rows)`` iterations in blocks of ``SMALL_BLOCK`` per cooperative launch (tv_small_cp): x, p, q updated in place; TV of the
         iterate each dual update saw -> slot 0, 1/2 |x_new - x0|^2 -> slot F (the slots the kernel pair fills)."""
         ws = self._small_ws()
-        n, done = rows.shape[0], 0
-        if rows.stride(1) != 1:
-            raise ValueError("rows must be a (n, SLOTS) fp64 tensor with contiguous rows")
-        while done < n:
-            k = min(self.SMALL_BLOCK, n - done)
+
+        def launch(k, row_ptr):
             # the reduction that closes the launch writes TV -> slot 0 and the fidelity -> slot F of the rows themselves
             _nv.check(self.lib.tv_small_cp(self.geo.ref, _nv.ptr(self.x), _nv.ptr(self.x0), _nv.ptr(self.p), _nv.ptr(self.q), self.sigma_D, self.reg,
-                                           self.tau, self.sigma_A, k, rows[done].data_ptr(), rows.stride(0), self.F, _nv.ptr(ws), self.stream))
-            done += k
+                                           self.tau, self.sigma_A, k, row_ptr, rows.stride(0), self.F, _nv.ptr(ws), self.stream))
             self.it += k
 
-    def _run_graphed_from(self, hist, first, n_iter):
-        """Capture GRAPH_BLOCK iterations (not executed during capture) and replay them over hist[first:]."""
-        K = self.GRAPH_BLOCK
-        nrep = (n_iter - first) // K
-        if nrep < 1:
-            return 0
-        it0, x_ref, xalt_ref, q_ref, qalt_ref = self.it, self.x, self.x_alt, self.q, self.q_alt
-        try:
-            buf = torch.zeros((K, self.SLOTS), dtype=torch.float64, device=self.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for k in range(K):
-                    self.step(buf[k])
-        except Exception:
-            self.it, self.x, self.x_alt, self.q, self.q_alt = it0, x_ref, xalt_ref, q_ref, qalt_ref      # nothing ran: undo the bookkeeping, stay eager
-            return 0
-        self.it = it0
-        done = 0
-        for r in range(nrep):
-            graph.replay()
-            hist[first + done:first + done + K].copy_(buf)
-            done += K
-            self.it += K
-        return done
+        self._small_blocks(rows, launch)
 
-    def result(self):
-        """The iterate as a DENSE (Nz, M, Ny, Nx) tensor: with padded state (``pitch``) a contiguous copy -- callers that ``.view(-1)``
-        it, take its ``data_ptr()`` or hand it to the dense ``tv_*`` entry points must not see pad columns (round-4 advice); ``.x``
-        stays the raw (possibly strided) view of the solver's storage."""
-        return self.x.contiguous() if self.pitch != (0, 0) else self.x
+    _ROLES = ("it", "x", "x_alt", "q", "q_alt")
+
+    def _run_graphed_from(self, hist, first, n_iter):
+        done = super()._run_graphed_from(hist, first, n_iter)
+        self.it += done                  # (the capture left the counter where it was)
+        return done
 
 
 # =================================================================================================
@@ -992,8 +1041,7 @@ class ChambollePockOperator(_SlabProblem):
             _nv.check(self.lib.tv_cpop_fused(g.ref, _nv.ptr(self.x), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
                                              _nv.ptr(atp), _nv.ptr(self.x_new), self.sigma_D, self.reg, self.tau, 0, -1,
                                              out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))
-            h = self.plan.exchange_grad(self.q, self.qh_prev[0] if self.qh_prev is not None else None,
-                                        self.qh_next[0] if self.qh_next is not None else None)
+            h = self.plan.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next))
             s.wait(h)
             _nv.check(self.lib.tv_cpop_fixup(g.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x_new),
                                              self.tau, 0, -1, _nv.ptr(self.ws), self.stream))
@@ -1003,8 +1051,7 @@ class ChambollePockOperator(_SlabProblem):
         s.wait(h)
         _nv.check(self.lib.tv_cp_dual(g.ref, _nv.ptr(self.x), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
                                       self.sigma_D, self.reg, out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))
-        h = self.plan.exchange_grad(self.q, self.qh_prev[0] if self.qh_prev is not None else None,
-                                    self.qh_next[0] if self.qh_next is not None else None)
+        h = self.plan.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next))
         atp = self._apply(self.AT, self.p, self.x.shape, "AT(p)")             # the user's operator runs while the q halos travel
         self.n_AT += 1
         s.wait(h)
@@ -1020,12 +1067,6 @@ class ChambollePockOperator(_SlabProblem):
         self.slab.allreduce_sum_(hist)
         h = hist.cpu().numpy()
         return h[:, 1] + self.reg * h[:, 0]
-
-    def result(self):
-        """The iterate as a DENSE (Nz, M, Ny, Nx) tensor: with padded state (``pitch``) a contiguous copy -- callers that ``.view(-1)``
-        it, take its ``data_ptr()`` or hand it to the dense ``tv_*`` entry points must not see pad columns (round-4 advice); ``.x``
-        stays the raw (possibly strided) view of the solver's storage."""
-        return self.x.contiguous() if self.pitch != (0, 0) else self.x
 
 
 # =================================================================================================
@@ -1083,20 +1124,7 @@ class SubgradientDescent(_SlabProblem):
         self._scratch = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
         self.placement = None
         if self.one_pass:
-            img_bytes = self.x.numel() * self.x.element_size()
-            if tune_placement is None:
-                free, _total = torch.cuda.mem_get_info(self.device)
-                tune_placement = img_bytes >= (4 << 30) and free >= 3 * img_bytes + (8 << 30)      # slabs too: local launches only
-            if tune_placement:
-                keep = (self.x, self.x_alt, self.x0)
-                try:
-                    self._tune_placement()
-                except RuntimeError as exc:       # an optimisation, never a failure (out of memory while holding the candidates, ...)
-                    self.x, self.x_alt, self.x0 = keep
-                    self.x.copy_(self.x0)
-                    torch.cuda.empty_cache()
-                    self.placement = {"error": str(exc)[:200]}
-                del keep
+            self._pp_tune(tune_placement, True, ("x", "x_alt", "x0"), self._tune_placement)
 
     def _tune_placement(self, n_extra=2, reps=2):
         """Pick where the two image buffers of the x ping-pong (and x0) live by MEASUREMENT, as ``ChambollePock._tune_x_placement``
@@ -1109,56 +1137,26 @@ class SubgradientDescent(_SlabProblem):
         t_begin = _time.perf_counter()
         nz = self.slab.nz
         out = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
-        hp = self.xh_prev if self.xh_prev is not None else None
-        hn = self.xh_next if self.xh_next is not None else None
 
-        def one(i_buf, o_buf):
-            self.x, self.x_alt = i_buf, o_buf
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            self._one_pass_range(0, nz, hp, hn, out[0:1], out[3:4])
-            b.record()
-            return a, b
-
-        def round_trip(u, v):
-            evs = [(one(u, v), one(v, u)) for _ in range(reps)]
-            torch.cuda.synchronize(self.device)
-            return min(e[0][0].elapsed_time(e[0][1]) for e in evs) + min(e[1][0].elapsed_time(e[1][1]) for e in evs)
+        def launch():
+            self._one_pass_range(0, nz, self.xh_prev, self.xh_next, out[0:1], out[3:4])
 
         x_a, x_b = self.x, self.x_alt
         for _ in range(2):                                                   # warm-up (code load, clocks)
-            one(x_a, x_b)
+            self._pp_one(launch, x_a, x_b)
         cands = [x_a, x_b] + [self.new_image() for _ in range(n_extra)]
         for c in cands[1:]:
             c.copy_(self.x0)                                                 # every candidate holds data of the problem's kind (no denormals, no NaN)
-        n = len(cands)
-        ev = [[[] for _ in range(n)] for _ in range(n)]
-        for r in range(reps):
-            for i in range(n):
-                for j in range(n):
-                    if i != j:
-                        ev[i][j].append(one(cands[i], cands[j]))
-        torch.cuda.synchronize(self.device)
-        t = [[(min(a.elapsed_time(b) for a, b in ev[i][j]) if i != j else float("inf")) for j in range(n)] for i in range(n)]
-        _, bi, bj = min(((t[i][j] + t[j][i], i, j) for i in range(n) for j in range(i + 1, n)))
-        info = {"candidates": n, "step_ms": [[None if i == j else round(t[i][j], 3) for j in range(n)] for i in range(n)],
-                "chosen": [bi, bj], "chosen_ms": [round(t[bi][bj], 3), round(t[bj][bi], 3)], "first_pair_ms": [round(t[0][1], 3), round(t[1][0], 3)]}
+        ms, (bi, bj), chosen_ms, first_ms = self._pp_pairs(launch, cands, reps)
+        info = {"candidates": len(cands), "step_ms": ms, "chosen": [bi, bj], "chosen_ms": chosen_ms, "first_pair_ms": first_ms}
         x_a, x_b = cands[bi], cands[bj]
         spare = [c for k, c in enumerate(cands) if k not in (bi, bj)]
         del cands
-        if spare:                                                            # x0 (read once per step): the caller's array against a copy
-            x0_orig, x0_copy = self.x0, spare[0]
-            x0_copy.copy_(x0_orig)
-            t0_ = round_trip(x_a, x_b)
-            self.x0 = x0_copy
-            t1_ = round_trip(x_a, x_b)
-            info["x0_round_trip_ms"] = [round(t0_, 3), round(t1_, 3)]
-            if t0_ <= t1_:
-                self.x0 = x0_orig
-            del x0_orig, x0_copy
+        if spare:
+            info["x0_round_trip_ms"] = self._pp_x0(launch, x_a, x_b, spare[0], reps)
         del spare
         self.x, self.x_alt = x_a, x_b
-        self.x.copy_(self.x0)
+        self._reset_state()
         torch.cuda.synchronize(self.device)
         torch.cuda.empty_cache()
         info["seconds"] = round(_time.perf_counter() - t_begin, 3)
@@ -1206,12 +1204,7 @@ class SubgradientDescent(_SlabProblem):
             self._small_check()
             return self.loss_from_slots(hist.cpu().numpy(), self.reg)
         use_graph = (self.x0.numel() <= self.GRAPH_MAX_VOXELS) if graph is None else bool(graph)
-        start = 0
-        if use_graph and not self.slab.sharded and n_iter >= 2 + 2 * self.GRAPH_BLOCK:
-            self.step(hist[0])
-            self.step(hist[1])
-            start = 2 + self._run_graphed_from(hist, 2, n_iter)
-        for it in range(start, n_iter):
+        for it in range(self._run_graphed_head(hist, use_graph), n_iter):
             self.step(hist[it])
         self.slab.allreduce_sum_(hist)
         return self.loss_from_slots(hist.cpu().numpy(), self.reg)
@@ -1220,45 +1213,16 @@ class SubgradientDescent(_SlabProblem):
         """``len(rows)`` descent steps in blocks of ``SMALL_BLOCK`` per cooperative launch (tv_small_subgrad_descent); TV(x_k) -> slot 0,
         1/2 |x_{k+1} - x0|^2 -> slot 3.  The iterate is ping-ponged: after an odd block x and x_alt trade places."""
         ws = self._small_ws()
-        n, done = rows.shape[0], 0
-        while done < n:
-            k = min(self.SMALL_BLOCK, n - done)
+
+        def launch(k, row_ptr):
             _nv.check(self.lib.tv_small_subgrad_descent(self.geo.ref, _nv.ptr(self.x), _nv.ptr(self.x_alt), _nv.ptr(self.x0), _nv.ptr(self.norms_ext),
-                                                        self.step_size, self.reg, k, rows[done].data_ptr(), rows.stride(0), 3, _nv.ptr(ws), self.stream))
+                                                        self.step_size, self.reg, k, row_ptr, rows.stride(0), 3, _nv.ptr(ws), self.stream))
             if k & 1:
                 self.x, self.x_alt = self.x_alt, self.x
-            done += k
 
-    def _run_graphed_from(self, hist, first, n_iter):
-        """Capture GRAPH_BLOCK iterations (not executed during capture) and replay them over hist[first:]."""
-        K = self.GRAPH_BLOCK
-        nrep = (n_iter - first) // K
-        if nrep < 1:
-            return 0
-        x_ref, xalt_ref = self.x, getattr(self, "x_alt", None)
-        try:
-            buf = torch.zeros((K, self.SLOTS), dtype=torch.float64, device=self.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for k in range(K):
-                    self.step(buf[k])
-        except Exception:
-            self.x = x_ref                                 # nothing ran: undo the bookkeeping, stay eager
-            if xalt_ref is not None:
-                self.x_alt = xalt_ref
-            return 0
-        done = 0
-        for r in range(nrep):
-            graph.replay()
-            hist[first + done:first + done + K].copy_(buf)
-            done += K
-        return done
+        self._small_blocks(rows, launch)
 
-    def result(self):
-        """The iterate as a DENSE (Nz, M, Ny, Nx) tensor: with padded state (``pitch``) a contiguous copy -- callers that ``.view(-1)``
-        it, take its ``data_ptr()`` or hand it to the dense ``tv_*`` entry points must not see pad columns (round-4 advice); ``.x``
-        stays the raw (possibly strided) view of the solver's storage."""
-        return self.x.contiguous() if self.pitch != (0, 0) else self.x
+    _ROLES = ("x", "x_alt")         # (x_alt: the one-pass kernel and the persistent loop only)
 
 
 # =================================================================================================
@@ -1384,6 +1348,7 @@ class ADMM(_SlabProblem):
             self._tune_placement()
 
     _STATE = ("x", "_zt", "u", "b", "r", "d", "Ad")      # the arrays an outer iteration streams through
+    _ROLES = ("x", "d", "Ad", "b", "r", "_have_r", "u", "u_alt")
 
     # ---- what the x-solve of one outer iteration moves (bench.py's roofline_xsolve) ----------------------------------------------
     @property
@@ -1600,8 +1565,7 @@ class ADMM(_SlabProblem):
         if self.single:          # the first array IS t = z - u
             h = s.exchange(send_prev=self._zt[0, self.ch_fwd] if self.plan.g_send_prev else None,
                            send_next=self._zt[nz - 1, self.ch_back] if self.plan.g_send_next else None,
-                           recv_prev=self.wh_prev[0] if self.wh_prev is not None else None,
-                           recv_next=self.wh_next[0] if self.wh_next is not None else None)
+                           recv_prev=_plane0(self.wh_prev), recv_next=_plane0(self.wh_next))
             s.wait(h)
             _nv.check(lib.tv_DT_axpy(g.ref, _nv.ptr(self._zt), None, _nv.ptr(self.wh_prev), _nv.ptr(self.wh_next),
                                      _nv.ptr(self.x0), self.rho, _nv.ptr(self.b), self.stream))
@@ -1669,8 +1633,7 @@ class ADMM(_SlabProblem):
         # the boundary planes of t' travel to the neighbours (as those of t = z - u do in _rhs)
         h = s.exchange(send_prev=self._zt[0, self.ch_fwd] if self.plan.g_send_prev else None,
                        send_next=self._zt[nz - 1, self.ch_back] if self.plan.g_send_next else None,
-                       recv_prev=self.wh_prev[0] if self.wh_prev is not None else None,
-                       recv_next=self.wh_next[0] if self.wh_next is not None else None)
+                       recv_prev=_plane0(self.wh_prev), recv_next=_plane0(self.wh_next))
         s.wait(h)
         _nv.check(lib.tv_admm_fixup(g.ref, _nv.ptr(self._zt), _nv.ptr(self.wh_prev), _nv.ptr(self.wh_next), _nv.ptr(self.r), self.rho,
                                     0, -1, self.rr[1:2].data_ptr(), _nv.ptr(self.ws), self.stream))
@@ -1756,15 +1719,13 @@ class ADMM(_SlabProblem):
         K = self.n_cg
         alpha = (ctypes.c_double * K)(*[c[0] for c in self._cheb_coef])
         beta = (ctypes.c_double * K)(*[c[1] for c in self._cheb_coef])
-        n, done = rows.shape[0], 0
-        if rows.stride(1) != 1:
-            raise ValueError("rows must be a (n, 2) fp64 tensor with contiguous rows")
-        while done < n:
-            k = min(self.SMALL_BLOCK, n - done)
+
+        def launch(k, row_ptr):
             _nv.check(self.lib.tv_small_admm(self.geo.ref, _nv.ptr(self.x), _nv.ptr(self.x0), _nv.ptr(self._zt), _nv.ptr(self.u), _nv.ptr(self.r),
                                              _nv.ptr(self.d), _nv.ptr(self.Ad), _nv.ptr(self._small_grad), self.rho, self.reg / self.rho, alpha, beta,
-                                             K, k, rows[done].data_ptr(), rows.stride(0), 1, _nv.ptr(ws), self.stream))
-            done += k
+                                             K, k, row_ptr, rows.stride(0), 1, _nv.ptr(ws), self.stream))
+
+        self._small_blocks(rows, launch)
 
     def run(self, n_outer, graph=None):
         """n_outer outer iterations; returns the loss history.  graph: None = replay blocks of GRAPH_BLOCK outer iterations
@@ -1779,50 +1740,8 @@ class ADMM(_SlabProblem):
             h = hist.cpu().numpy()
             return 0.5 * h[:, 1] + self.reg * h[:, 0]
         use_graph = (self.x0.numel() <= self.GRAPH_MAX_VOXELS) if graph is None else bool(graph)
-        start = 0
-        if use_graph and not self.slab.sharded and n_outer >= 2 + 2 * self.GRAPH_BLOCK:
-            self.step(hist[0])                   # eager: also the warm-up of the capture
-            self.step(hist[1])
-            start = 2 + self._run_graphed_from(hist, 2, n_outer)
-        for k in range(start, n_outer):
+        for k in range(self._run_graphed_head(hist, use_graph), n_outer):
             self.step(hist[k])
         self.slab.allreduce_sum_(hist)
         h = hist.cpu().numpy()
         return 0.5 * h[:, 1] + self.reg * h[:, 0]
-
-    def _run_graphed_from(self, hist, first, n_outer):
-        """Capture GRAPH_BLOCK outer iterations (not executed during capture) and replay them over hist[first:]."""
-        K = self.GRAPH_BLOCK
-        nrep = (n_outer - first) // K
-        if nrep < 1:
-            return 0
-        # the Chebyshev x-solve REBINDS x / d / Ad / b at Python level inside every step (the new image is written next to the old
-        # one and the roles are swapped): a capture that fails part-way must not leave them pointing at buffers whose kernels
-        # never ran (round-3 advice; ChambollePock._run_graphed_from does the same for x / x_alt)
-        saved = (self.x, self.d, self.Ad, self.b, self.r, self._have_r)
-        saved_u = (self.u, self.u_alt)
-        try:
-            buf = torch.zeros((K, 2), dtype=torch.float64, device=self.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for k in range(K):
-                    self.step(buf[k])
-        except Exception:
-            self.x, self.d, self.Ad, self.b, self.r, self._have_r = saved
-            self.u, self.u_alt = saved_u
-            return 0                             # nothing ran: undo the bookkeeping, stay eager
-        if (self.x is not saved[0]) or (self.d is not saved[1]) or (self.Ad is not saved[2]) or (self.b is not saved[3]) or (self.u is not saved_u[0]):
-            # the block does not return the buffers to their roles (odd number of role swaps): replaying it would not be the
-            # same iteration twice -- cannot happen with GRAPH_BLOCK even, checked all the same
-            self.x, self.d, self.Ad, self.b, self.r, self._have_r = saved
-            self.u, self.u_alt = saved_u
-            return 0
-        done = 0
-        for r in range(nrep):
-            graph.replay()
-            hist[first + done:first + done + K].copy_(buf)
-            done += K
-        return done
-
-    def result(self):
-        return self.x

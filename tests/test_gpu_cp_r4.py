@@ -2,7 +2,8 @@
 
   * q ping-pong (tv_cp_sweep with q_in != q_out): the same arithmetic on the same values -- bit-identical x, q, loss;
   * lagged fidelity (TV_CP_FID_OF_INPUT; the fix-up reads no x0): the same iterates bit for bit, the loss history equal to the
-    last digits (the fidelity is one fp64 sum over all sites instead of two partial sums), and equal to the oracle's.
+    last digits (the fidelity is one fp64 sum over all sites instead of two partial sums), and equal to the oracle's;
+  * hipGraph replay (``run(graph=True)``) of the three solvers' loops: the eager loop's history and state, also when the capture fails part-way.
 """
 import os
 
@@ -154,3 +155,108 @@ def test_arena_option_changes_nothing_but_the_buffers(shape, pitch):
     assert torch.equal(a.result(), b.result()) and torch.equal(a.q, b.q) and torch.equal(a.p, b.p)
     np.testing.assert_allclose(lb, la, rtol=1e-13)
     assert torch.equal(x0, keep)
+
+
+# ---- hipGraph replay of the loops (``run(graph=True)``): small volumes take the persistent kernels by default, so nothing else forces it -------
+GRAPH_CASES = [(True, (3, 2, 16, 64), np.float32),                       # one-sweep kernel (64: the smallest width it takes)
+               (False, (3, 2, 9, 20), np.float32), (False, (3, 2, 9, 20), np.float64)]      # the kernel pair
+GRAPH_KW = dict(scheme="hybrid", reg_z_over_reg=1.0, reg_time=1.3)
+N_GRAPHED = 25                                                           # 2 eager + 2 replays of GRAPH_BLOCK = 10 + 3 in the tail
+
+
+def _graph_x0(shape, dtype):
+    import torch
+    rng = np.random.default_rng(13)
+    return torch.as_tensor((orc.phantom(shape, dtype=np.float64) + 100 * rng.random(shape)).astype(dtype)).cuda()
+
+
+def _cp(fused, shape, dtype):
+    import pytv
+    return pytv.solvers.ChambollePock(_graph_x0(shape, dtype), 20.0, fused=fused, persistent=None if fused else False, **GRAPH_KW)
+
+
+_cp_eager_runs = {}
+
+
+def _cp_eager(fused, shape, dtype):
+    """(solver, loss history) of ``run(N_GRAPHED, graph=False)``: computed once per case, compared against and left unchanged"""
+    key = (fused, shape, dtype)
+    if key not in _cp_eager_runs:
+        a = _cp(fused, shape, dtype)
+        _cp_eager_runs[key] = (a, a.run(N_GRAPHED, graph=False))
+    return _cp_eager_runs[key]
+
+
+def _assert_same_cp_run(fused, a, la, b, lb):
+    import torch
+    if fused:       # the eager block reports the fidelity through the lagged slots, the replayed steps through their own: one fp64 sum against two
+        np.testing.assert_allclose(lb, la, rtol=1e-12)
+    else:
+        assert np.array_equal(la, lb)
+    assert torch.equal(a.result(), b.result()) and torch.equal(a.q, b.q) and torch.equal(a.p, b.p)
+    assert a.it == N_GRAPHED and b.it == N_GRAPHED
+
+
+def _fail_second_captured_step(solver):
+    """``solver.step`` raises -- before it launches anything -- when it is called for the second time inside a stream capture: the abandoned
+    capture holds exactly one complete step (an odd number of buffer-role swaps).  Returns the counter of captured calls."""
+    import torch
+    real, seen = solver.step, [0]
+
+    def step(out=None):
+        if torch.cuda.is_current_stream_capturing():
+            seen[0] += 1
+            if seen[0] == 2:
+                raise RuntimeError("injected: the capture is abandoned before its second step")
+        return real(out)
+
+    solver.step = step
+    return seen
+
+
+@pytest.mark.parametrize("fused,shape,dtype", GRAPH_CASES)
+def test_cp_graph_replay_equals_the_eager_loop(fused, shape, dtype):
+    a, la = _cp_eager(fused, shape, dtype)
+    b = _cp(fused, shape, dtype)
+    assert b.fused == fused and not b.small
+    lb = b.run(N_GRAPHED, graph=True)
+    _assert_same_cp_run(fused, a, la, b, lb)
+
+
+@pytest.mark.parametrize("fused,shape,dtype", GRAPH_CASES)
+def test_cp_capture_that_fails_part_way_leaves_a_working_solver(fused, shape, dtype):
+    a, la = _cp_eager(fused, shape, dtype)
+    b = _cp(fused, shape, dtype)
+    seen = _fail_second_captured_step(b)
+    lb = b.run(N_GRAPHED, graph=True)
+    assert seen[0] == 2                                # the capture was begun, abandoned and not tried again
+    _assert_same_cp_run(fused, a, la, b, lb)
+
+
+@pytest.mark.parametrize("shape,dtype", [case[1:] for case in GRAPH_CASES])
+def test_descent_capture_that_fails_part_way_leaves_a_working_solver(shape, dtype):
+    import torch
+    import pytv
+    mk = lambda: pytv.solvers.SubgradientDescent(_graph_x0(shape, dtype), 20.0, 5e-3, persistent=False, **GRAPH_KW)      # noqa: E731
+    a, b = mk(), mk()
+    la = a.run(N_GRAPHED, graph=False)
+    seen = _fail_second_captured_step(b)
+    lb = b.run(N_GRAPHED, graph=True)
+    assert seen[0] == 2
+    assert np.array_equal(la, lb)
+    assert torch.equal(a.result(), b.result())
+
+
+@pytest.mark.parametrize("x_solver", ["chebyshev", "cg"])
+def test_admm_capture_that_fails_part_way_leaves_a_working_solver(x_solver):
+    import torch
+    import pytv
+    n = 2 + 2 * pytv.solvers.ADMM.GRAPH_BLOCK + 3
+    mk = lambda: pytv.solvers.ADMM(_graph_x0((3, 2, 16, 64), np.float32), 6.0, 0.1, n_cg=4, x_solver=x_solver, **GRAPH_KW)      # noqa: E731
+    a, b = mk(), mk()
+    la = a.run(n, graph=False)
+    seen = _fail_second_captured_step(b)
+    lb = b.run(n, graph=True)
+    assert seen[0] == 2
+    assert np.array_equal(la, lb)
+    assert torch.equal(a.result(), b.result()) and torch.equal(a.u, b.u) and torch.equal(a.z, b.z)

@@ -60,6 +60,10 @@ for name, make in (("sub-gradient descent, device resident", lambda: pytv.solver
     t0 = time.perf_counter()
     loss = solver.run(nb_it)
     print("%s:        %.3f s, loss %.4e -> %.4e" % (name, time.perf_counter() - t0, loss[0], loss[-1]))
+# how good is the answer?  (solver is the Chambolle-Pock one: its dual variable certifies the distance to the minimiser)
+primal, dual, gap = solver.duality_gap()
+print("Chambolle-Pock certificate: primal %.6e, dual %.6e, gap %.3e (relative %.1e): |x - x*|_2 <= %.3e" % (
+    primal, dual, gap, gap / primal, np.sqrt(2 * max(gap, 0.0))))
 estimate = solver.result().cpu().numpy()
 print("PSNR noisy %.2f dB -> denoised %.2f dB" % (
     10 * np.log10(255 ** 2 / np.mean((noisy - truth) ** 2)), 10 * np.log10(255 ** 2 / np.mean((estimate - truth) ** 2))))

@@ -182,6 +182,22 @@ int tv_cp_dual(const tv_geom* g, const void* x, const void* x_prev, const void* 
 int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x,
                  const void* x0, void* p, double tau, double sigma_A, double* fid, void* ws, void* stream);
 
+/* Duality-gap certificate of the model every solver here minimises, P(x) = 1/2 |x - x0|^2 + lambda |D x|_{2,1}, for an iterate x and a dual
+ * variable qs = qscale * q with |qs|_2 <= lambda per site (Chambolle-Pock: its q, qscale = 1; scaled-form ADMM: q = u, qscale = rho; both are
+ * projections).  Over the local planes, with gd = D^T qs:
+ *   out[0] = |D x|_{2,1}
+ *   out[1] = 1/2 |x - x0|^2
+ *   out[2] = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda |D x|_2 - <qs, D x> ]  =  P(x) - Dual(qs),  Dual(qs) = <gd, x0> - 1/2 |gd|^2
+ * out[2] is accumulated site by site in that cancellation-free form (both parts are >= 0 at every site of a feasible qs), never as P - Dual;
+ * it is not clamped: in fp32 a converged pair can come out slightly negative (absolute error of order eps * P).  The caller has
+ * P = out[1] + lambda * out[0], Dual = P - out[2], and by strong convexity 1/2 |x - x*|^2 <= out[2].
+ * REDUCE-ONLY: nothing is written except out (three device fp64 words) and ws.  x_prev / x_next as in tv_cp_dual, q_prev / q_next as in
+ * tv_DT (unscaled, like q); slab partials add up to the unsharded scalars.  lambda > 0 and a finite qscale != 0, else TV_E_ARG.
+ * Every geometry of tv_cp_dual / tv_cp_primal (four schemes, fp32 / fp64, pitched arrays, weight maps / volumes): one launch, Nd + 2 words per
+ * voxel; fp32 planes of >= 4 MiB (the plane-marching kernels' domain): a D^T-side and a D-side pass, 2 Nd + 5 words. */
+int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                const void* q_next, const void* x0, double lambda, double qscale, double* out, void* ws, void* stream);
+
 /* One-sweep form of the same iteration (all four schemes; fp32, nx % 4 == 0, nx >= 64,
  * any m: more than 8 frames are processed as time windows of 8): q is read and written ONCE per
  * iteration.  x is ping-ponged.

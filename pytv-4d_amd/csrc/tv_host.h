@@ -307,4 +307,10 @@ int DT_axpy(const tv_geom* g, const DG& d, const void* q, const void* qp, const 
             void* out, const void* base, double alpha, const void* base2 = nullptr, double beta = 0.0);
 int DT_cp_primal(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
                  float* x, const float* x0, float* p, float tau, float sigma_a, float inv_1p_sigma_a, double* partials);
+// duality gap, reduce-only (tv_dual_gap): the D^T-side pass writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2, the D-side pass (same
+// grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to the first pass's sums
+int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
+           const float* x, const float* x0, float qscale, double* partials);
+int D_gap(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
+          const float* q, const float* x0, float qscale, double lambda, double* p_tv, double* p_fid, double* p_gap);
 }  // namespace tvm

@@ -9,6 +9,7 @@
 //                AdmmZU   -> z/u update of ADMM                  (tv_admm_zu)
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
 //                StoreDT / AxpyDT / CpPrimal epilogues           (tv_DT, tv_DT_axpy, tv_cp_primal)
+//   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
 //   k_normal_vec  / k_normal_central_vec  : x + rho D^T D x from x alone   (tv_normal_op)
 //   k_gather : scalar reference evaluation of the last two (TV_SCALAR_GATHER=1)
@@ -53,6 +54,46 @@ __global__ __launch_bounds__(256) void k_DT(DG g, WT<T> w, Src src, Epi epi) {
         acc = block_sum(acc, sm);
         if (threadIdx.x == 0 && threadIdx.y == 0) epi.partials[linear_block_id()] = acc;
     }
+}
+
+// duality gap of (x, qs = qscale q), reduce-only (tv_dual_gap): a thread evaluates D x at its site with d_site's arithmetic and D^T qs at the
+// same site with dt_site's; the site's own samples of q are the same loads in both (nothing is stored in between: the compiler keeps one
+// copy).  Three sums per block: |D x|_2, 1/2 (x - x0)^2 and the site's gap term (tv_stencil.h, gap_terms).
+template <int S, typename T, int V> struct GapSite {
+    static constexpr bool REDUCES = true;
+    WT<T> w;
+    SrcScaled<T, V> src;
+    const T* x;
+    const T* x0;
+    double lambda;
+    double* acc3;        // the calling thread's three sums
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        long long inpl;
+        const Vec<T, V> gd = dt_site<S, T, V>(g, w, src, c, inpl);
+        const long long offd = (long long)c.zl * g.s_dz + inpl, off = (long long)c.zl * g.s_z + inpl;
+        Vec<T, V> qv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) qv[k] = vsplat<T, V>(T(0));
+        for_each_channel<S>(g, [&](auto slot, int ch) { qv[decltype(slot)::value] = src.ld(offd + (long long)ch * g.s_z); });
+        gap_terms<T, V>(o, qv, vload<T, V>(x + off), vload<T, V>(x0 + off), &gd, lambda, acc3[0], acc3[1], acc3[2]);
+        return 0.0;
+    }
+};
+template <int S, typename T, int V>
+__global__ __launch_bounds__(256) void k_gap(DG g, WT<T> w, const T* x, const T* xp, const T* xn, SrcScaled<T, V> src, const T* x0,
+                                              double lambda, double* p_tv, double* p_fid, double* p_gap) {
+    __shared__ double sm[16];
+    const Coord c = thread_coord<V>(g, 0);
+    double a[3] = {0.0, 0.0, 0.0};
+    d_site<S, T, V>(g, w, x, xp, xn, 1, c, GapSite<S, T, V>{w, src, x, x0, lambda, a}, PlainMem());
+    const long long b = linear_block_id();
+    const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
+    const double tv = block_sum(a[0], sm);
+    if (first) p_tv[b] = tv;
+    const double fid = block_sum(a[1], sm);
+    if (first) p_fid[b] = fid;
+    const double gap = block_sum(a[2], sm);
+    if (first) p_gap[b] = gap;
 }
 
 // =============================================================================================
@@ -915,6 +956,46 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
         hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimal<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
         HIP_TRY(hipGetLastError());
         return reduce_partials((double*)ws, lc.nblocks, nmax, fid, st);
+    });
+}
+
+// P(x) - Dual(qs) for qs = qscale q, with its two by-products; reduce-only (include/pytv4d.h)
+int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                const void* q_next, const void* x0, double lambda, double qscale, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (x == nullptr || q == nullptr || x0 == nullptr || out == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
+    if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
+    if (!(qscale != 0.0) || !std::isfinite(qscale)) return fail(TV_E_ARG, "qscale must be a finite number other than 0");
+    if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
+    if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, q_prev, q_next, x0, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const long long nmax = max_partials(d);
+    double* const w0 = (double*)ws;                       // |D x|_{2,1}
+    double* const w1 = w0 + nmax + kStage + 16;           // 1/2 |x - x0|^2
+    double* const w2 = w1 + nmax + kStage + 16;           // the gap
+    if (march_ok(g, d, vec) && d.m <= 8) {
+        // plane-marching form, two launches on the same grid: q is read by both (2 Nd + 5 words per voxel).  Not M = 16: the D-side
+        // kernel keeps 16 frames and their q samples in flight and spills (288 - 1540 bytes of scratch per lane)
+        long long nb_dt, nb;
+        if (int rc = tvm::DT_gap(g, d, q, q_prev, q_next, st, &nb_dt, (const float*)x, (const float*)x0, (float)qscale, w2)) return rc;
+        if (int rc = tvm::D_gap(g, d, x, x_prev, x_next, st, &nb, (const float*)q, (const float*)x0, (float)qscale, lambda, w0, w1, w2))
+            return rc;
+        if (nb != nb_dt) return fail(TV_E_ARG, "tv_dual_gap: the two marching passes disagree about the grid");
+        if (int rc = reduce_partials(w0, nb, nmax, out, st)) return rc;
+        if (int rc = reduce_partials(w1, nb, nmax, out + 1, st)) return rc;
+        return reduce_partials(w2, nb, nmax, out + 2, st);
+    }
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        SrcScaled<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next, (T)qscale};
+        hipLaunchKernelGGL((k_gap<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
+                           src, (const T*)x0, lambda, w0, w1, w2);
+        HIP_TRY(hipGetLastError());
+        if (int rc = reduce_partials(w0, lc.nblocks, nmax, out, st)) return rc;
+        if (int rc = reduce_partials(w1, lc.nblocks, nmax, out + 1, st)) return rc;
+        return reduce_partials(w2, lc.nblocks, nmax, out + 2, st);
     });
 }
 

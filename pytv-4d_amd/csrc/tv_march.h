@@ -180,6 +180,7 @@ __global__ __launch_bounds__(256, LIGHT ? 3 : ((PF || M > 8) ? 2 : 1)) void k_D_
         acc = block_sum(acc, sm);
         if (threadIdx.x == 0 && threadIdx.y == 0) epi.partials[linear_block_id()] = acc;
     }
+    if constexpr (requires { epi.finish(sm); }) epi.finish(sm);      // epilogues that keep sums of their own (GapD: three per block)
 }
 
 // =============================================================================================

@@ -30,6 +30,10 @@ int D_admm_zu(const tv_geom* g, const DG& d, const void* x, const void* xp, cons
               float* z, float* u, float thresh, double* partials, int tform) {
     return launch_D_march<AdmmZU>(g, d, x, xp, xn, st, nb, z, u, thresh, partials, tform);
 }
+int D_gap(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
+          const float* q, const float* x0, float qscale, double lambda, double* p_tv, double* p_fid, double* p_gap) {
+    return launch_D_march<GapD>(g, d, x, xp, xn, st, nb, q, x0, qscale, lambda, p_tv, p_fid, p_gap);
+}
 int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
             float* norms_ext, double* partials, int ghost_lo, int ghost_hi) {
     const int zc = march_zchunk(d);

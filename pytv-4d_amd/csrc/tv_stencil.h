@@ -463,6 +463,98 @@ template <typename T, int V> struct CpPrimal {
     }
 };
 
+// =============================================================================================
+// duality gap of 1/2 |x - x0|^2 + lambda |D x|_{2,1} at (x, qs = qscale q), reduce-only (tv_dual_gap): with gd = D^T qs
+//   gap = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda |D x|_2 - <qs, D x> ]      both parts >= 0 site by site for |qs|_2 <= lambda
+// Each site's term is formed from the T-valued stencil results and accumulated in fp64; nothing is stored.
+// =============================================================================================
+// the dual variable as the gather sees it: q scaled by a constant (ADMM: q = u, qscale = rho; Chambolle-Pock: 1)
+template <typename T, int V> struct SrcScaled {
+    const T* y;
+    const T* yp;
+    const T* yn;
+    T s;
+    __device__ __forceinline__ Vec<T, V> ld(long long off) const { return s * vload<T, V>(y + off); }
+    __device__ __forceinline__ T lds(long long off) const { return s * y[off]; }
+    __device__ __forceinline__ Vec<T, V> ldp(long long off) const { return s * vload<T, V>(yp + off); }
+    __device__ __forceinline__ Vec<T, V> ldn(long long off) const { return s * vload<T, V>(yn + off); }
+};
+// the three per-site terms from D x (slots o), the site's own samples of qs (slots qv), x, x0 and gd; sums over the V columns
+template <typename T, int V>
+__device__ __forceinline__ void gap_terms(const Vec<T, V> (&o)[8], const Vec<T, V> (&qv)[8], const Vec<T, V>& xv, const Vec<T, V>& x0v,
+                                          const Vec<T, V>* gd, double lambda, double& a_tv, double& a_fid, double& a_gap) {
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    Vec<T, V> dot = vsplat<T, V>(T(0));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dot = dot + qv[k] * o[k];              // inactive slots are exactly zero in o
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const T nrm = tsqrt(ds.v[i]);
+        const double e = (double)xv.v[i] - (double)x0v.v[i];
+        a_tv += (double)nrm;
+        a_fid += 0.5 * e * e;
+        a_gap += lambda * (double)nrm - (double)dot.v[i];
+        if (gd != nullptr) {
+            const double r = e + (double)gd->v[i];
+            a_gap += 0.5 * r * r;
+        }
+    }
+}
+// D-side pass of the plane-marching form (k_D_march): |D x|_{2,1}, 1/2 |x - x0|^2 and sum (lambda |D x|_2 - <qs, D x>); reads x0 and q once.
+// The D^T-side pass (GapDT) ran BEFORE it on the same grid and left its per-block sums in `partials`: finish() adds to them.
+template <int S, typename T, int V> struct GapD {
+    static constexpr bool REDUCES = false;       // three sums, written by finish()
+    const T* q;
+    const T* x0;
+    T qscale;
+    double lambda;
+    double* p_tv;
+    double* p_fid;
+    double* partials;     // the gap sums (the name k_D_march expects of an epilogue)
+    double a_tv = 0.0, a_fid = 0.0, a_gap = 0.0;
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8], const Vec<T, V>& xc) {
+        const long long inpl = (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        const T* base = q + (long long)c.zl * g.s_dz + inpl;
+        Vec<T, V> qv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) qv[k] = vsplat<T, V>(T(0));
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            qv[decltype(slot)::value] = qscale * vload_s<T, V>(base + (long long)ch * g.s_z);
+        });
+        const Vec<T, V> x0v = vload_s<T, V>(x0 + (long long)c.zl * g.s_z + inpl);
+        gap_terms<T, V>(o, qv, xc, x0v, nullptr, lambda, a_tv, a_fid, a_gap);
+        return 0.0;
+    }
+    __device__ __forceinline__ void finish(double* sm) {
+        const long long b = linear_block_id();
+        const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
+        const double tv = block_sum(a_tv, sm);
+        if (first) p_tv[b] = tv;
+        const double fid = block_sum(a_fid, sm);
+        if (first) p_fid[b] = fid;
+        const double gap = block_sum(a_gap, sm);
+        if (first) partials[b] = partials[b] + gap;
+    }
+};
+// D^T-side pass of the plane-marching form (k_DT_march): sum 1/2 (x - x0 + qscale D^T q)^2; reads x and x0 once
+template <typename T, int V> struct GapDT {
+    static constexpr bool REDUCES = true;
+    const T* x;
+    const T* x0;
+    T qscale;
+    double* partials;
+    __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
+        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const double e = ((double)xv.v[i] - (double)x0v.v[i]) + (double)(qscale * r.v[i]);
+            acc += 0.5 * e * e;
+        }
+        return acc;
+    }
+};
+
 // One axis of the gather.  MODE 0: y^(p-e) - y^(p)   (adjoint of a forward difference)
 //                          MODE 1: y^(p) - y^(p+e)   (adjoint of a backward difference)
 //                          MODE 2: y^(p-e) - y^(p+e) (adjoint of a central difference)

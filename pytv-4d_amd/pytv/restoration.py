@@ -13,11 +13,13 @@ from .tv_operators_GPU import _to_device
 __all__ = ["denoise_tv_chambolle"]
 
 
-def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10):
+def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None):
     """Total-variation denoising of a 2-D (rows, cols) or 3-D (planes, rows, cols) image.
 
     weight : denoising weight (larger = smoother), as in scikit-image.
     eps    : stop when the relative change of the objective over ``check_every`` iterations drops below eps.
+    rel_gap: None (the default) = the rule above; a number = stop when the duality gap certifies the answer instead,
+             gap <= rel_gap * objective at a check (``ChambollePock.run_until``: 1/2 |u - u*|^2 <= gap); ``eps`` is then ignored.
     Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point."""
     was_torch = isinstance(image, torch.Tensor)
     x, _ = _to_device(image)
@@ -29,6 +31,9 @@ def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, sch
         raise ValueError("denoise_tv_chambolle: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
     cp = ChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0)
     prev, done = None, 0
+    if rel_gap is not None:
+        cp.run_until(rel_gap, max_num_iter, check_every)
+        done = max_num_iter
     while done < max_num_iter:
         n = min(check_every, max_num_iter - done)
         loss = cp.run(n)

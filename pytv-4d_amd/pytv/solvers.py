@@ -408,6 +408,55 @@ class _SlabProblem:
             self.x0 = x0_orig
         return [round(t0, 3), round(t1, 3)]
 
+    # ---- duality-gap certificate (tv_dual_gap; ChambollePock / ADMM: the solvers that carry a dual variable) ----------------------------------
+    _GAP_DOC = """For P(x) = 1/2 |x - x0|^2 + reg |D x|_{2,1} and any dual variable q with |q|_2 <= reg per site,
+        Dual(q) = <D^T q, x0> - 1/2 |D^T q|^2 <= P(x*) <= P(x), and by strong convexity 1/2 |x - x*|^2 <= P(x) - Dual(q): the gap bounds the
+        distance to the minimiser, not the progress of the loop.  The kernel (tv_dual_gap) sums it site by site in its cancellation-free form
+        1/2 (x - x0 + D^T q)^2 + (reg |D x|_2 - <q, D x>), both parts >= 0, and writes nothing but three scalars.
+        fp32 FLOOR: the cancellation inside reg |D x|_2 - <q, D x> leaves an absolute error of order eps_fp32 * P, so relative gaps below
+        about 1e-6 are not resolvable in fp32; the gap may then come out slightly negative (it is not clamped) and ``run_until`` ends on
+        its iteration limit with ``converged=False``."""
+
+    def _gap_certificate(self, x, q, qscale):
+        """(primal, dual, gap) of the iterate x and the dual variable qscale * q as Python floats, global over all ranks: one exchange of the
+        boundary planes of x and q (buffers of its own: the loop's halo planes, slots and lagged-fidelity block are not touched), one
+        tv_dual_gap on this rank's planes, one all-reduce of the three scalars."""
+        pl, s = self.plan, self.slab
+        b = getattr(self, "_gap_buf", None)
+        if b is None:
+            b = self._gap_buf = dict(out=torch.zeros(3, dtype=torch.float64, device=self.device),
+                                     xp=self.new_plane() if pl.x_need_prev else None, xn=self.new_plane() if pl.x_need_next else None,
+                                     qp=self.new_plane() if pl.g_need_prev else None, qn=self.new_plane() if pl.g_need_next else None)
+        s.wait(pl.exchange_image(x, b["xp"], b["xn"]))
+        s.wait(pl.exchange_grad(q, _plane0(b["qp"]), _plane0(b["qn"])))
+        out = b["out"]
+        _nv.check(self.lib.tv_dual_gap(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]), _nv.ptr(b["qn"]),
+                                       _nv.ptr(self.x0), self.reg, float(qscale), out.data_ptr(), _nv.ptr(self.ws), self.stream))
+        s.allreduce_sum_(out)
+        tv, fid, gap = (float(v) for v in out.cpu().tolist())
+        primal = fid + self.reg * tv
+        return primal, primal - gap, gap
+
+    def _run_until_gap(self, rel_gap, max_n, check_every):
+        """``run`` in blocks of ``check_every`` until gap <= rel_gap * max(|primal|, tiny) at a check or ``max_n`` iterations are done."""
+        import numpy as np
+        rel_gap, max_n, check_every = float(rel_gap), int(max_n), int(check_every)
+        if check_every < 1 or max_n < 0:
+            raise ValueError("run_until: check_every must be >= 1 and the iteration limit >= 0")
+        tiny = float(np.finfo(np.float64).tiny)
+        losses, done = [], 0
+        while True:
+            n = min(check_every, max_n - done)
+            if n > 0:
+                losses.append(np.asarray(self.run(n), dtype=np.float64))
+                done += n
+            primal, dual, gap = self.duality_gap()
+            converged = gap <= rel_gap * max(abs(primal), tiny)
+            if converged or done >= max_n:
+                break
+        info = dict(iterations=done, primal=primal, dual=dual, gap=gap, converged=bool(converged), error_bound=float(np.sqrt(2.0 * max(gap, 0.0))))
+        return (np.concatenate(losses) if losses else np.zeros(0)), info
+
     def _reset_state(self):
         """Back to the state of a fresh solver in the arrays that are bound now."""
         self.x.copy_(self.x0)
@@ -942,6 +991,22 @@ class ChambollePock(_SlabProblem):
             self.it += k
 
         self._small_blocks(rows, launch)
+
+    def duality_gap(self):
+        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats -- on every path (kernel pair, one-sweep,
+        persistent), between ``run`` / ``run_steps`` calls; the state of the loop is not touched.  Sharded: collective, every rank calls it
+        and gets the same numbers.
+        """
+        return self._gap_certificate(self.x, self.q, 1.0)
+    duality_gap.__doc__ += _SlabProblem._GAP_DOC
+
+    def run_until(self, rel_gap, max_iter, check_every=10):
+        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
+        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
+        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
+        """
+        return self._run_until_gap(rel_gap, max_iter, check_every)
+    run_until.__doc__ += _SlabProblem._GAP_DOC
 
     _ROLES = ("it", "x", "x_alt", "q", "q_alt")
 
@@ -1745,3 +1810,19 @@ class ADMM(_SlabProblem):
         self.slab.allreduce_sum_(hist)
         h = hist.cpu().numpy()
         return 0.5 * h[:, 1] + self.reg * h[:, 0]
+
+    def duality_gap(self):
+        """(primal, dual, gap) of the current iterate x and the dual variable rho * u as Python floats (u = v - shrink(v, reg / rho) is the
+        projection of v onto the ball of radius reg / rho: rho * u is feasible by construction), between ``run`` / ``step`` calls, on every
+        path; the state of the loop is not touched.  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._gap_certificate(self.x, self.u, self.rho)
+    duality_gap.__doc__ += _SlabProblem._GAP_DOC
+
+    def run_until(self, rel_gap, max_outer, check_every=5):
+        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` outer iterations, stopping at the first check where
+        gap <= rel_gap * max(|primal|, tiny), or after ``max_outer`` outer iterations.  Returns (loss_history, info); info: ``iterations``,
+        ``primal``, ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
+        """
+        return self._run_until_gap(rel_gap, max_outer, check_every)
+    run_until.__doc__ += _SlabProblem._GAP_DOC

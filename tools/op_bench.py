@@ -56,7 +56,13 @@ for scheme in schemes:
         ("tv_DT_axpy", 2 * nd + 2, lambda: nv.check(lib.tv_DT_axpy(g.ref, nv.ptr(d), nv.ptr(u), None, None, nv.ptr(x), 0.1, nv.ptr(o), st))),
         ("tv_cp_dual", 1 + 2 * nd, lambda: nv.check(lib.tv_cp_dual(g.ref, nv.ptr(x), None, None, nv.ptr(d), 0.5, 25.0, nv.ptr(sc), nv.ptr(ws), st))),
         ("tv_cp_primal", nd + 5, lambda: nv.check(lib.tv_cp_primal(g.ref, nv.ptr(d), None, None, nv.ptr(o), nv.ptr(x), nv.ptr(o2), 0.05, 1.0, nv.ptr(sc), nv.ptr(ws), st))),
+        # reduce-only duality gap of (x, q) against x0: the one-site kernel moves nd + 2 words, the plane-marching form (fp32 planes of
+        # >= 4 MiB, M <= 8, no weight volume: what this shape takes by default) reads q in both of its passes: 2 nd + 5
+        ("tv_dual_gap", (2 * nd + 5) if (x.dtype == torch.float32 and shape[1] <= 8 and shape[2] * shape[3] * shape[1] * 4 >= (4 << 20)
+                                         and shape[3] >= 128 and shape[3] % 4 == 0 and "weight_dev" not in kw) else nd + 2,
+         lambda: nv.check(lib.tv_dual_gap(g.ref, nv.ptr(x), None, None, nv.ptr(u), None, None, nv.ptr(o2), 25.0, 1.0, gap3.data_ptr(), nv.ptr(ws), st))),
     ]
+    gap3 = torch.zeros(3, dtype=torch.float64, device=dev)
     wvol = 1 if "weight_dev" in kw else 0          # one more word per voxel wherever the time channels are formed
 
     def cp_sweep():
@@ -82,7 +88,7 @@ for scheme in schemes:
         ops.append(("admm_sweep+fixup", 3 + 2 * nd + wvol, admm_sweep))
         ops.append(("cpop_sweep+fixup", 3 + 2 * nd + wvol, cpop_sweep))
     if wvol:
-        ops = [(n, wd + (1 if n in ("tv_D", "tv_subgrad_fused", "tv_subgrad_fused_norms", "tv_cp_dual", "tv_subgrad", "tv_admm_zu") else 0), f) for n, wd, f in ops]
+        ops = [(n, wd + (1 if n in ("tv_D", "tv_subgrad_fused", "tv_subgrad_fused_norms", "tv_cp_dual", "tv_subgrad", "tv_admm_zu", "tv_dual_gap") else 0), f) for n, wd, f in ops]
     only = [o for o in os.environ.get("OPS", "").split(",") if o]
     for name, words, f in ops:
         if (only and name not in only) or f is None:

@@ -3,9 +3,6 @@
 
 TV_FUSED_INSTANTIATE(float, ALG_CP)
 
-// every M <= 8 has its own instantiation; more frames run as time windows of CP_TWN = 8 frames (tv_fused.h)
-static bool fused_m_ok(int m) { return m >= 1; }
-
 // planes per z-chunk of the one-sweep path (sweep, fix-up and the host's interior-first schedule share it): its blocks are
 // CP_TR rows x CP_BC columns, half as many per plane as the marching kernels' -- with march_zchunk's rule (round 1) BASELINE
 // config 2 ran on 8-plane chunks and config 1 on 16, 3 - 5 % slower than with 16 - 32 / 32 - 64 (tools/ab_cp.py --shape).
@@ -42,7 +39,7 @@ int subgrad_pass2(const tv_geom* g, const DG& d, const void* x, const void* xp, 
                   const float* norms_ext, float* G) {
     const int zc = march_zchunk(d);
     const LC lc = march_cfg(d, zc);
-    return dispatch_fused(g->scheme, d.m, [&]<int S, int M>() -> int {
+    return dispatch_scheme_m(WindowedMs{}, g->scheme, d.m, kNoFusedSM, [&]<int S, int M>() -> int {
         if constexpr (S != CENTRAL && M >= 1) {
             hipLaunchKernelGGL((k_subgrad_march<S, M>), lc.grid, lc.block, 0, st, d, make_w<float>(g), (const float*)x,
                                (const float*)xp, (const float*)xn, norms_ext, G, zc);
@@ -59,12 +56,10 @@ int subgrad_pass2(const tv_geom* g, const DG& d, const void* x, const void* xp, 
 struct SweepPlan {
     LC lc;
     int zc, chunk0;
-    long long nmax;
     bool xw, force_win;
 };
-static int sweep_plan(const tv_geom* g, const DG& d, const void* x_in, const void* x_prev, const void* x_next, int64_t chunk_begin,
-                      int64_t chunk_count, SweepPlan& sp, bool& empty) {
-    sp.nmax = max_partials(d);
+static int sweep_plan(const tv_geom* g, const DG& d, const Partials& P, const void* x_in, const void* x_prev, const void* x_next,
+                      int64_t chunk_begin, int64_t chunk_count, SweepPlan& sp, bool& empty) {
     sp.zc = fused_zchunk(d);
     const int zc = sp.zc;
     {   // halos are only needed by the chunks that touch the slab boundary
@@ -90,7 +85,7 @@ static int sweep_plan(const tv_geom* g, const DG& d, const void* x_in, const voi
     lc.grid.y = (unsigned)chunk_count;
     lc.grid.z = (unsigned)nwin;
     lc.nblocks = (long long)lc.grid.x * chunk_count * nwin;
-    if (lc.nblocks > sp.nmax) return fail(TV_E_ARG, "internal: sweep partials exceed the workspace");
+    if (lc.nblocks > P.nmax) return fail(TV_E_ARG, "internal: sweep partials exceed the workspace");
     sp.chunk0 = (int)chunk_begin;
     sp.xw = env_int("TV_FUSED_XW", 1) != 0;
     // M == 8, hybrid: the windowed instantiation (one window) needs 234 VGPRs and no scratch where the plain one sits at
@@ -102,9 +97,8 @@ static int sweep_plan(const tv_geom* g, const DG& d, const void* x_in, const voi
 }
 
 // launch geometry of the fix-up over the local planes [z_begin, z_begin + z_count) (count < 0: all)
-static int fixup_plan(const tv_geom* g, const DG& d, const void* q, const void* q_prev, const void* q_next, int64_t z_begin, int64_t z_count,
-                      FixPlan& fp, long long& nmax, bool& empty) {
-    nmax = max_partials(d);
+static int fixup_plan(const tv_geom* g, const DG& d, const Partials& P, const void* q, const void* q_prev, const void* q_next, int64_t z_begin,
+                      int64_t z_count, FixPlan& fp, bool& empty) {
     const int zc = fused_zchunk(d);
     if (z_count < 0) { z_begin = 0; z_count = d.nz; }
     if (z_begin < 0 || z_begin + z_count > d.nz) return fail(TV_E_ARG, "plane range outside the slab");
@@ -128,8 +122,51 @@ static int fixup_plan(const tv_geom* g, const DG& d, const void* q, const void* 
     fp.n1 = d.za ? (long long)fp.g1.x * fp.g1.y * fp.g1.z : 0;
     fp.n2 = (long long)fp.g2.x * fp.g2.y * fp.g2.z;
     fp.n3 = nwin > 0 ? (long long)fp.g3.x * fp.g3.y * fp.g3.z : 0;
-    if (fp.n0 + fp.n1 + fp.n2 + fp.n3 > nmax) return fail(TV_E_ARG, "internal: fix-up partials exceed the workspace");
+    if (fp.n0 + fp.n1 + fp.n2 + fp.n3 > P.nmax) return fail(TV_E_ARG, "internal: fix-up partials exceed the workspace");
     fp.chunk_lo = chunk_lo; fp.zc = zc; fp.zb = zb; fp.zn = zn; fp.xw = xw;
+    return 0;
+}
+
+// The frame of the one-sweep entry points, after their own argument checks: plan the launch over the chunk range (an empty range zeroes the
+// outputs), launch ALG's sweep for the dtype with the arguments that make_args.operator()<T>(P) builds, then reduce slot 0 into *tvout and
+// the slots 1 .. nsum into sums[0 .. nsum) (nsum may be 0).
+template <int ALG, typename MakeArgs>
+static int run_sweep(const tv_geom* g, const DG& d, const void* x_in, const void* x_prev, const void* x_next, int64_t chunk_begin,
+                     int64_t chunk_count, void* ws, hipStream_t st, double* tvout, double* sums, int nsum, MakeArgs&& make_args) {
+    const Partials P(ws, d);
+    SweepPlan sp;
+    bool empty = false;
+    if (int rc = sweep_plan(g, d, P, x_in, x_prev, x_next, chunk_begin, chunk_count, sp, empty)) return rc;
+    if (empty) {
+        HIP_TRY(hipMemsetAsync(tvout, 0, sizeof(double), st));
+        if (nsum > 0) HIP_TRY(hipMemsetAsync(sums, 0, nsum * sizeof(double), st));
+        return 0;
+    }
+    if (int rc = dispatch_dtype(g->dtype, [&]<typename T>() -> int {
+            return tvm::fused_sweep<T, ALG>(g, d, sp.lc, st, make_args.template operator()<T>(P), sp.zc, sp.chunk0, sp.xw, sp.force_win);
+        }))
+        return rc;
+    if (int rc = P.reduce(0, sp.lc.nblocks, tvout, st)) return rc;
+    for (int k = 0; k < nsum; ++k)
+        if (int rc = P.reduce(1 + k, sp.lc.nblocks, sums + k, st)) return rc;
+    return 0;
+}
+
+// The same for the fix-up over a range of planes: one sum (slot 0) into *out, or, when the caller says the sum means nothing, *out = 0.
+template <int ALG, typename MakeArgs>
+static int run_fixup(const tv_geom* g, const DG& d, const void* q, const void* q_prev, const void* q_next, int64_t z_begin, int64_t z_count,
+                     Partials P, hipStream_t st, double* out, bool has_sum, MakeArgs&& make_args) {
+    FixPlan fp;
+    bool empty = false;
+    if (int rc = fixup_plan(g, d, P, q, q_prev, q_next, z_begin, z_count, fp, empty)) return rc;
+    if (!empty) {
+        if (int rc = dispatch_dtype(g->dtype, [&]<typename T>() -> int {
+                return tvm::fused_fixup<T, ALG>(g, d, st, make_args.template operator()<T>(fp), fp, P.slot(0));
+            }))
+            return rc;
+        if (has_sum) return P.reduce(0, fp.n0 + fp.n1 + fp.n2 + fp.n3, out, st);
+    }
+    HIP_TRY(hipMemsetAsync(out, 0, sizeof(double), st));
     return 0;
 }
 
@@ -140,7 +177,7 @@ int tv_cp_fused_supported(const tv_geom* g) {
     if (make_dg(g, d, true)) return 0;
     // fp32, and fp64 since round 3 (2 columns per lane); a dense array needs whole lanes, a pitched one has them by construction
     // (the last lane of a ragged row holds pad columns: zeros in, zeros out -- round 4)
-    if ((!d.pitched && d.nx % d.vl != 0) || d.nx < 64 || !fused_m_ok(d.m)) return 0;
+    if ((!d.pitched && d.nx % d.vl != 0) || d.nx < 64) return 0;
     if (d.m > CP_TWN && env_int("TV_NO_FUSED_TWIN", 0)) return 0;
     // frames below 2^31 bytes: per-lane byte offsets are 32-bit, the PFX prefetch addresses x0 / p through a per-frame buffer descriptor
     // (num_records = frame bytes as a 32-bit number: 2^32 would wrap to 0) and BUF_OOB = 0x80000000 must lie outside the frame (round-5 advice)
@@ -157,7 +194,22 @@ int tv_cp_zchunk(const tv_geom* g) {
 
 static int cp_sweep_impl(const tv_geom* g, const void* x_in, const void* x_prev, const void* x_next, const void* q_in, void* q, const void* x0,
                          void* p, void* x_out, double sigma_D, double lambda, double tau, double sigma_A, int32_t flags, int64_t chunk_begin,
-                         int64_t chunk_count, double* tvout, double* fid, void* ws, void* stream);
+                         int64_t chunk_count, double* tvout, double* fid, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (!x_in || !q || !x0 || !p || !x_out || !tvout || !fid || !ws) return fail(TV_E_ARG, "NULL array");
+    if (x_in == x_out) return fail(TV_E_ARG, "x_in and x_out must be different buffers (ping-pong)");
+    if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
+    if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
+    if (!aligned16({x_in, x_prev, x_next, q, x0, p, x_out, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
+    auto args = [&]<typename T>(const Partials& P) {          // slot 2, the second fidelity: TV_CP_FID_BOTH only
+        return FusedArgsT<T>{(const T*)x_in, (const T*)x_prev, (const T*)x_next, (T*)q, (const T*)x0, (T*)p,
+                             (T*)x_out, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), P.slot(0), P.slot(1),
+                             ((flags & TV_CP_FID_OF_INPUT) ? 2 : 0) | ((flags & TV_CP_FID_BOTH) ? 4 : 0), (const T*)(q_in ? q_in : q), P.slot(2)};
+    };
+    return run_sweep<ALG_CP>(g, d, x_in, x_prev, x_next, chunk_begin, chunk_count, ws, (hipStream_t)stream, tvout, fid,
+                             (flags & TV_CP_FID_BOTH) ? 2 : 1, args);
+}
 
 int tv_cp_fused(const tv_geom* g, const void* x_in, const void* x_prev, const void* x_next, void* q, const void* x0,
                 void* p, void* x_out, double sigma_D, double lambda, double tau, double sigma_A, int64_t chunk_begin,
@@ -175,42 +227,6 @@ int tv_cp_sweep(const tv_geom* g, const void* x_in, const void* x_prev, const vo
     return cp_sweep_impl(g, x_in, x_prev, x_next, q_in, q_out, x0, p, x_out, sigma_D, lambda, tau, sigma_A, flags, chunk_begin, chunk_count, tvout, fid, ws, stream);
 }
 
-static int cp_sweep_impl(const tv_geom* g, const void* x_in, const void* x_prev, const void* x_next, const void* q_in, void* q, const void* x0,
-                         void* p, void* x_out, double sigma_D, double lambda, double tau, double sigma_A, int32_t flags, int64_t chunk_begin,
-                         int64_t chunk_count, double* tvout, double* fid, void* ws, void* stream) {
-    DG d;
-    if (int rc = make_dg(g, d, true)) return rc;
-    if (!x_in || !q || !x0 || !p || !x_out || !tvout || !fid || !ws) return fail(TV_E_ARG, "NULL array");
-    if (x_in == x_out) return fail(TV_E_ARG, "x_in and x_out must be different buffers (ping-pong)");
-    if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
-    if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
-    if (!aligned16({x_in, x_prev, x_next, q, x0, p, x_out, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    SweepPlan sp;
-    bool empty = false;
-    if (int rc = sweep_plan(g, d, x_in, x_prev, x_next, chunk_begin, chunk_count, sp, empty)) return rc;
-    if (empty) {
-        HIP_TRY(hipMemsetAsync(tvout, 0, sizeof(double), st));
-        HIP_TRY(hipMemsetAsync(fid, 0, ((flags & TV_CP_FID_BOTH) ? 2 : 1) * sizeof(double), st));
-        return 0;
-    }
-    double* w0 = (double*)ws;
-    double* w1 = w0 + sp.nmax + kStage + 16;
-    double* w2 = w1 + sp.nmax + kStage + 16;          // third partial array (tv_workspace_bytes): TV_CP_FID_BOTH only
-    auto sweep = [&]<typename T>() -> int {
-        FusedArgsT<T> a{(const T*)x_in, (const T*)x_prev, (const T*)x_next, (T*)q, (const T*)x0, (T*)p,
-                        (T*)x_out, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), w0, w1,
-                        ((flags & TV_CP_FID_OF_INPUT) ? 2 : 0) | ((flags & TV_CP_FID_BOTH) ? 4 : 0), (const T*)(q_in ? q_in : q), w2};
-        return tvm::fused_sweep<T, ALG_CP>(g, d, sp.lc, st, a, sp.zc, sp.chunk0, sp.xw, sp.force_win);
-    };
-    const int rc = (g->dtype == TV_F32) ? sweep.template operator()<float>() : sweep.template operator()<double>();
-    if (rc) return rc;
-    if (int r2 = reduce_partials(w0, sp.lc.nblocks, sp.nmax, tvout, st)) return r2;
-    if (int r3 = reduce_partials(w1, sp.lc.nblocks, sp.nmax, fid, st)) return r3;
-    if (flags & TV_CP_FID_BOTH) return reduce_partials(w2, sp.lc.nblocks, sp.nmax, fid + 1, st);
-    return 0;
-}
-
 int tv_cp_fixup(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x_out, const void* x0,
                 double tau, int64_t z_begin, int64_t z_count, double* fid, void* ws, void* stream) {
     DG d;
@@ -218,26 +234,11 @@ int tv_cp_fixup(const tv_geom* g, const void* q, const void* q_prev, const void*
     if (!q || !x_out || !fid || !ws) return fail(TV_E_ARG, "NULL array");      // x0 may be NULL: no fidelity (*fid = 0)
     if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
     if (!aligned16({q, q_prev, q_next, x_out, x0})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    FixPlan fp;
-    long long nmax = 0;
-    bool empty = false;
-    if (int rc = fixup_plan(g, d, q, q_prev, q_next, z_begin, z_count, fp, nmax, empty)) return rc;
-    if (empty) {
-        HIP_TRY(hipMemsetAsync(fid, 0, sizeof(double), st));
-        return 0;
-    }
-    double* w0 = (double*)ws;
-    auto fix = [&]<typename T>() -> int {
-        FixupArgsT<T> a{(const T*)q, (const T*)q_prev, (const T*)q_next, (T*)x_out, (const T*)x0, (T)tau, fp.chunk_lo};
-        return tvm::fused_fixup<T, ALG_CP>(g, d, st, a, fp, w0);
-    };
-    if (int rc = (g->dtype == TV_F32) ? fix.template operator()<float>() : fix.template operator()<double>()) return rc;
-    if (x0 == nullptr) {                 // no fidelity asked for (tv_cp_sweep with TV_CP_FID_OF_INPUT delivers it): the partials are meaningless
-        HIP_TRY(hipMemsetAsync(fid, 0, sizeof(double), st));
-        return 0;
-    }
-    return reduce_partials(w0, fp.n0 + fp.n1 + fp.n2 + fp.n3, nmax, fid, st);
+    // x0 == NULL: no fidelity asked for (tv_cp_sweep with TV_CP_FID_OF_INPUT delivers it), the partials are meaningless
+    return run_fixup<ALG_CP>(g, d, q, q_prev, q_next, z_begin, z_count, Partials(ws, d), (hipStream_t)stream, fid, x0 != nullptr,
+                             [&]<typename T>(const FixPlan& fp) {
+                                 return FixupArgsT<T>{(const T*)q, (const T*)q_prev, (const T*)q_next, (T*)x_out, (const T*)x0, (T)tau, fp.chunk_lo};
+                             });
 }
 
 // One-sweep ADMM (tv_fused.h, ALG_ADMM): the z / u update of the outer iteration that ends and the residual of the x-solve that
@@ -261,51 +262,31 @@ int tv_admm_sweep(const tv_geom* g, const void* x, const void* x_prev, const voi
     if (!(thresh >= 0.0)) return fail(TV_E_ARG, "thresh must be >= 0");
     if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
     if (!aligned16({x, x_prev, x_next, u_in, u, t, x0, r, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    SweepPlan sp;
-    bool empty = false;
-    if (int rc = sweep_plan(g, d, x, x_prev, x_next, chunk_begin, chunk_count, sp, empty)) return rc;
-    if (empty) {
-        HIP_TRY(hipMemsetAsync(tvout, 0, sizeof(double), st));
-        HIP_TRY(hipMemsetAsync(rr, 0, sizeof(double), st));
-        return 0;
-    }
-    double* w0 = (double*)ws;
-    double* w1 = w0 + sp.nmax + kStage + 16;
-    auto sweep = [&]<typename T>() -> int {
-        FusedArgsT<T> a{(const T*)x, (const T*)x_prev, (const T*)x_next, (T*)u, (const T*)x0, (T*)t,
-                        (T*)r, (T)thresh, (T)0, (T)rho, (T)0, (T)0, w0, w1, (int)(full_store & 3), (const T*)u_in};
-        return tvm::fused_sweep<T, ALG_ADMM>(g, d, sp.lc, st, a, sp.zc, sp.chunk0, sp.xw, sp.force_win);
-    };
-    const int rc = (g->dtype == TV_F32) ? sweep.template operator()<float>() : sweep.template operator()<double>();
-    if (rc) return rc;
-    if (int r2 = reduce_partials(w0, sp.lc.nblocks, sp.nmax, tvout, st)) return r2;
-    return reduce_partials(w1, sp.lc.nblocks, sp.nmax, rr, st);
+    return run_sweep<ALG_ADMM>(g, d, x, x_prev, x_next, chunk_begin, chunk_count, ws, (hipStream_t)stream, tvout, rr, 1, [&]<typename T>(const Partials& P) {
+        return FusedArgsT<T>{(const T*)x, (const T*)x_prev, (const T*)x_next, (T*)u, (const T*)x0, (T*)t,
+                             (T*)r, (T)thresh, (T)0, (T)rho, (T)0, (T)0, P.slot(0), P.slot(1), (int)(full_store & 3), (const T*)u_in};
+    });
+}
+
+// rr == NULL (tv_cpop_fixup): nobody reads the sum, it goes to a spare word behind slot 1
+static int admm_fixup_impl(const tv_geom* g, const DG& d, const void* t, const void* t_prev, const void* t_next, void* r, double rho,
+                           int64_t z_begin, int64_t z_count, double* rr, void* ws, void* stream) {
+    if (!t || !r || !ws) return fail(TV_E_ARG, "NULL array");
+    if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
+    if (!aligned16({t, t_prev, t_next, r})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
+    const Partials P(ws, d);
+    return run_fixup<ALG_ADMM>(g, d, t, t_prev, t_next, z_begin, z_count, P, (hipStream_t)stream, rr ? rr : P.spare(2, -1), true,
+                               [&]<typename T>(const FixPlan& fp) {
+                                   return FixupArgsT<T>{(const T*)t, (const T*)t_prev, (const T*)t_next, (T*)r, nullptr, (T)(-rho), fp.chunk_lo};
+                               });
 }
 
 int tv_admm_fixup(const tv_geom* g, const void* t, const void* t_prev, const void* t_next, void* r, double rho, int64_t z_begin,
                   int64_t z_count, double* rr, void* ws, void* stream) {
     DG d;
     if (int rc = make_dg(g, d, true)) return rc;
-    if (!t || !r || !rr || !ws) return fail(TV_E_ARG, "NULL array");
-    if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
-    if (!aligned16({t, t_prev, t_next, r})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    FixPlan fp;
-    long long nmax = 0;
-    bool empty = false;
-    if (int rc = fixup_plan(g, d, t, t_prev, t_next, z_begin, z_count, fp, nmax, empty)) return rc;
-    if (empty) {
-        HIP_TRY(hipMemsetAsync(rr, 0, sizeof(double), st));
-        return 0;
-    }
-    double* w0 = (double*)ws;
-    auto fix = [&]<typename T>() -> int {
-        FixupArgsT<T> a{(const T*)t, (const T*)t_prev, (const T*)t_next, (T*)r, nullptr, (T)(-rho), fp.chunk_lo};
-        return tvm::fused_fixup<T, ALG_ADMM>(g, d, st, a, fp, w0);
-    };
-    if (int rc = (g->dtype == TV_F32) ? fix.template operator()<float>() : fix.template operator()<double>()) return rc;
-    return reduce_partials(w0, fp.n0 + fp.n1 + fp.n2 + fp.n3, nmax, rr, st);
+    if (rr == nullptr) return fail(TV_E_ARG, "NULL array");
+    return admm_fixup_impl(g, d, t, t_prev, t_next, r, rho, z_begin, z_count, rr, ws, stream);
 }
 
 // One-sweep Chambolle-Pock with a data-fidelity operator (tv_fused.h, ALG_CPOP): q <- proj(q + sigma_D D x_in) and
@@ -319,24 +300,11 @@ int tv_cpop_fused(const tv_geom* g, const void* x_in, const void* x_prev, const 
     if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
     if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
     if (!aligned16({x_in, x_prev, x_next, q, atp, x_out, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    SweepPlan sp;
-    bool empty = false;
-    if (int rc = sweep_plan(g, d, x_in, x_prev, x_next, chunk_begin, chunk_count, sp, empty)) return rc;
-    if (empty) {
-        HIP_TRY(hipMemsetAsync(tvout, 0, sizeof(double), st));
-        return 0;
-    }
-    double* w0 = (double*)ws;
-    double* w1 = w0 + sp.nmax + kStage + 16;
-    auto sweep = [&]<typename T>() -> int {
-        FusedArgsT<T> a{(const T*)x_in, (const T*)x_prev, (const T*)x_next, (T*)q, nullptr, (T*)const_cast<void*>(atp),
-                        (T*)x_out, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)0, (T)1, w0, w1, 0, (const T*)q};
-        return tvm::fused_sweep<T, ALG_CPOP>(g, d, sp.lc, st, a, sp.zc, sp.chunk0, sp.xw, sp.force_win);
-    };
-    const int rc = (g->dtype == TV_F32) ? sweep.template operator()<float>() : sweep.template operator()<double>();
-    if (rc) return rc;
-    return reduce_partials(w0, sp.lc.nblocks, sp.nmax, tvout, st);
+    // (the kernel writes fidelity partials to slot 1 as every sweep does; here they mean nothing and are not reduced)
+    return run_sweep<ALG_CPOP>(g, d, x_in, x_prev, x_next, chunk_begin, chunk_count, ws, (hipStream_t)stream, tvout, nullptr, 0, [&]<typename T>(const Partials& P) {
+        return FusedArgsT<T>{(const T*)x_in, (const T*)x_prev, (const T*)x_next, (T*)q, nullptr, (T*)const_cast<void*>(atp),
+                             (T*)x_out, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)0, (T)1, P.slot(0), P.slot(1), 0, (const T*)q};
+    });
 }
 
 // its fix-up: x_out -= tau (missing adjoint terms); the ALG_ADMM instantiation with the coefficient tau (r += rho ... with rho = -tau)
@@ -344,11 +312,7 @@ int tv_cpop_fixup(const tv_geom* g, const void* q, const void* q_prev, const voi
                   int64_t z_count, void* ws, void* stream) {
     DG d;
     if (int rc = make_dg(g, d, true)) return rc;
-    if (ws == nullptr) return fail(TV_E_ARG, "NULL array");
-    // the fix-up's reduction (unused here) goes to the last word of the workspace: the pad behind the second partial array, which
-    // this call does not use
-    double* unused = (double*)ws + 2 * (max_partials(d) + kStage + 16) - 1;
-    return tv_admm_fixup(g, q, q_prev, q_next, x_out, -tau, z_begin, z_count, unused, ws, stream);
+    return admm_fixup_impl(g, d, q, q_prev, q_next, x_out, -tau, z_begin, z_count, nullptr, ws, stream);
 }
 
 }  // extern "C"

@@ -14,25 +14,7 @@ struct FixPlan {
     bool xw;
 };
 
-template <typename F> static int dispatch_fused(int scheme, int m, F&& f) {
-#define TV_CASE_F(SC)                                              \
-    case SC:                                                       \
-        switch (m) {                                               \
-            case 0: return f.template operator()<SC, 0>();         \
-            case 1: return f.template operator()<SC, 1>();         \
-            case 2: return f.template operator()<SC, 2>();         \
-            case 3: return f.template operator()<SC, 3>();         \
-            case 4: return f.template operator()<SC, 4>();         \
-            case 5: return f.template operator()<SC, 5>();         \
-            case 6: return f.template operator()<SC, 6>();         \
-            case 7: return f.template operator()<SC, 7>();         \
-            case 8: return f.template operator()<SC, 8>();         \
-        }                                                          \
-        break;
-    switch (scheme) { TV_CASE_F(0) TV_CASE_F(1) TV_CASE_F(2) TV_CASE_F(3) }
-#undef TV_CASE_F
-    return fail(TV_E_ARG, "unsupported (scheme, M) for the one-sweep path");
-}
+inline constexpr const char* kNoFusedSM = "unsupported (scheme, M) for the one-sweep path";
 
 // the sweep: every M <= 8 has its own instantiation, more frames run as time windows of CP_TWN = 8 frames (M == 0 below).
 // ADMM is built with the in-block column hand-off only (XW; TV_FUSED_XW=0 is a debugging switch of the CP sweep).
@@ -40,7 +22,7 @@ template <typename T, int ALG>
 static int fused_sweep_launch(const tv_geom* g, const DG& d, const LC& lc, hipStream_t st, const FusedArgsT<T>& a, int zc, int chunk0, bool xw,
                               bool force_win) {
     if (ALG != ALG_CP && !xw) return fail(TV_E_ARG, "the ADMM / operator sweeps are built with TV_FUSED_XW=1 only");
-    return dispatch_fused(g->scheme, (d.m > CP_TWN || force_win) ? 0 : d.m, [&]<int S, int M>() -> int {
+    return dispatch_scheme_m(WindowedMs{}, g->scheme, (d.m > CP_TWN || force_win) ? 0 : d.m, kNoFusedSM, [&]<int S, int M>() -> int {
         if constexpr (M == 0) {          // M > 8: windows of 8 frames
             if (xw) hipLaunchKernelGGL((k_cp_fused<S, CP_TWN, true, true, T, ALG>), lc.grid, lc.block, 0, st, d, make_w<T>(g), a, zc, chunk0);
             else if constexpr (ALG == ALG_CP)
@@ -57,24 +39,20 @@ template <typename T, int ALG>
 static int fused_fixup_launch(const tv_geom* g, const DG& d, hipStream_t st, const FixupArgsT<T>& a, const FixPlan& p, double* w0) {
     if (ALG != ALG_CP && !p.xw) return fail(TV_E_ARG, "the ADMM / operator sweeps are built with TV_FUSED_XW=1 only");
     const dim3 blk(64, 4, 1);
-    auto launch = [&]<int S, bool XW>() -> int {
-        if constexpr (ALG == ALG_CP || XW) {
-            hipLaunchKernelGGL((k_cp_fixup<S, 0, XW, T, ALG>), p.g0, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0);
-            if (d.za) hipLaunchKernelGGL((k_cp_fixup<S, 1, XW, T, ALG>), p.g1, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0);
-            hipLaunchKernelGGL((k_cp_fixup<S, 2, XW, T, ALG>), p.g2, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0 + p.n1);
-            if (p.n3 > 0)
-                hipLaunchKernelGGL((k_cp_fixup<S, 3, XW, T, ALG>), p.g3, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0 + p.n1 + p.n2);
-            HIP_TRY(hipGetLastError());
-        }
-        return 0;
-    };
-    const bool xw = p.xw;
-    switch (g->scheme) {
-        case TV_UPWIND: return xw ? launch.template operator()<UPWIND, true>() : launch.template operator()<UPWIND, false>();
-        case TV_DOWNWIND: return xw ? launch.template operator()<DOWNWIND, true>() : launch.template operator()<DOWNWIND, false>();
-        case TV_CENTRAL: return xw ? launch.template operator()<CENTRAL, true>() : launch.template operator()<CENTRAL, false>();
-        default: return xw ? launch.template operator()<HYBRID, true>() : launch.template operator()<HYBRID, false>();
-    }
+    return dispatch_scheme(g->scheme, [&]<int S>() -> int {
+        auto launch = [&]<bool XW>() -> int {
+            if constexpr (ALG == ALG_CP || XW) {
+                hipLaunchKernelGGL((k_cp_fixup<S, 0, XW, T, ALG>), p.g0, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0);
+                if (d.za) hipLaunchKernelGGL((k_cp_fixup<S, 1, XW, T, ALG>), p.g1, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0);
+                hipLaunchKernelGGL((k_cp_fixup<S, 2, XW, T, ALG>), p.g2, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0 + p.n1);
+                if (p.n3 > 0)
+                    hipLaunchKernelGGL((k_cp_fixup<S, 3, XW, T, ALG>), p.g3, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0 + p.n1 + p.n2);
+                HIP_TRY(hipGetLastError());
+            }
+            return 0;
+        };
+        return p.xw ? launch.template operator()<true>() : launch.template operator()<false>();
+    });
 }
 
 // one definition per (dtype, ALG), each in its own translation unit

@@ -1,9 +1,18 @@
 // tv_host.h -- host-side helpers shared by the translation units of libpytv4d_hip.so:
-// error reporting, tv_geom -> DG, launch geometry, partial-sum reduction, dispatch tables.
+//   fail / hipfail / HIP_TRY     error reporting
+//   make_dg, make_w              tv_geom -> DG / weights
+//   launch_cfg, march_cfg        launch geometry
+//   Partials                     the reduction scratch of tv_workspace_bytes(): its layout and the two-level reduction
+//   dispatch*                    run-time scheme / M / dtype / lane width -> template arguments
+//   g_options, env_int           the option table
+//   plane_big_enough, march_ok   which kernel family a geometry takes
+//   check_x_halos[2], check_y_halos   halo rules
+//   namespace tvm                launchers defined in the other translation units
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +20,7 @@
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <utility>
 
 #include "../../include/pytv4d.h"
 #include "tv_device.h"
@@ -112,7 +122,6 @@ inline LC launch_cfg(const DG& d, int V, int planes) {
 static const int kFlatBlocks = 2048;    // grid-stride kernels: 256 CUs x 8 blocks
 static const int kStage = 256;          // second-level partials
 
-// layout of the scratch buffer: [partials ... nmax][stage kStage]
 inline long long max_partials(const DG& d) {
     LC lc = launch_cfg(d, 1, d.nz + 2);
     // the one-sweep fix-up launches up to four classes whose block counts add up to ~3 x (256-column tiles) x (4-row
@@ -123,17 +132,37 @@ inline long long max_partials(const DG& d) {
     return n > kFlatBlocks ? n : kFlatBlocks;
 }
 
-inline int reduce_partials(double* ws, long long n, long long nmax, double* result, hipStream_t st) {
-    if (n <= 4096) {
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, st, ws, n, result);
-    } else {
-        double* stage = ws + nmax;
-        hipLaunchKernelGGL(k_reduce, dim3(kStage), dim3(256), 0, st, ws, n, stage);
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, st, stage, (long long)kStage, result);
+// The reduction scratch of tv_workspace_bytes(): kSlots independent arrays of [nmax per-block partials][kStage second-level
+// partials][pad 16].  An entry point builds ONE view per call (max_partials is not free) and passes it by value.
+struct Partials {
+    double* base;
+    long long nmax;
+    static constexpr int kSlots = 3;        // most sums one call reduces: tv_dual_gap, tv_cp_sweep with TV_CP_FID_BOTH
+    Partials(void* ws, const DG& d) : base((double*)ws), nmax(max_partials(d)) {}
+    long long slot_words() const { return nmax + kStage + 16; }
+    static size_t bytes(const DG& d) { return (size_t)(kSlots * Partials(nullptr, d).slot_words()) * sizeof(double); }
+    double* slot(int k) const { return base + k * slot_words(); }          // k < kSlots
+    // A word of the workspace that this call's reductions do not touch, for a total nobody reads: a caller that reduces through
+    // the slots below k only may use the first two words of slot k (i = 0, 1) or the pad in front of it (-16 <= i < 0).
+    double* spare(int k, int i = 0) const {
+        assert(k >= 1 && k < kSlots && i >= -16 && i <= 1);
+        return slot(k) + i;
     }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+    // *result = sum of the first n partials of slot k (deterministic tree; above 4096 in two levels through the slot's stage words)
+    int reduce(int k, long long n, double* result, hipStream_t st) const {
+        if (n > nmax) return fail(TV_E_ARG, "internal: partials exceed the workspace");
+        double* const w = slot(k);
+        if (n <= 4096) {
+            hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, st, w, n, result);
+        } else {
+            double* stage = w + nmax;
+            hipLaunchKernelGGL(k_reduce, dim3(kStage), dim3(256), 0, st, w, n, stage);
+            hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, st, stage, (long long)kStage, result);
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
 
 inline bool aligned16(std::initializer_list<const void*> ps) {
     for (const void* p : ps)
@@ -141,7 +170,6 @@ inline bool aligned16(std::initializer_list<const void*> ps) {
     return true;
 }
 
-// call f.template operator()<S, T, V>() for the run-time (scheme, dtype, vec)
 // lanes of a 16-byte vector for this dtype: `vec` at the call sites means "Nx is a multiple of it and every
 // pointer is 16-byte aligned"
 inline int vec_lanes(const tv_geom* g) { return g->dtype == TV_F32 ? 4 : 2; }
@@ -149,20 +177,42 @@ inline int vec_lanes(const tv_geom* g) { return g->dtype == TV_F32 ? 4 : 2; }
 // the row pitch is one by construction (make_dg), the last lane of a row then holds pad columns (zeros in, zeros out)
 inline bool rows_vectorisable(const tv_geom* g, const DG& d) { return d.pitched || d.nx % vec_lanes(g) == 0; }
 
-template <typename F> inline int dispatch(int scheme, int dtype, bool vec, F&& f) {
-#define TV_CASE(SC)                                                                  \
-    case SC:                                                                         \
-        if (dtype == TV_F32) {                                                       \
-            if (vec) return f.template operator()<SC, float, 4>();                   \
-            return f.template operator()<SC, float, 1>();                            \
-        }                                                                            \
-        if (vec) return f.template operator()<SC, double, 2>();                      \
-        return f.template operator()<SC, double, 1>();
+// ---- run-time value -> template argument: f is a generic lambda, called as f.template operator()<...>() ------------------
+template <typename F> inline int dispatch_scheme(int scheme, F&& f) {
     switch (scheme) {
-        TV_CASE(0) TV_CASE(1) TV_CASE(2) TV_CASE(3)
+        case UPWIND: return f.template operator()<UPWIND>();
+        case DOWNWIND: return f.template operator()<DOWNWIND>();
+        case CENTRAL: return f.template operator()<CENTRAL>();
+        case HYBRID: return f.template operator()<HYBRID>();
     }
-#undef TV_CASE
     return fail(TV_E_ARG, "unknown scheme");
+}
+template <typename F> inline int dispatch_dtype(int dtype, F&& f) {
+    return (dtype == TV_F32) ? f.template operator()<float>() : f.template operator()<double>();
+}
+// f.template operator()<S, T, V>() for the run-time (scheme, dtype, vec): V = the dtype's 16-byte lanes or 1
+template <typename F> inline int dispatch(int scheme, int dtype, bool vec, F&& f) {
+    return dispatch_scheme(scheme, [&]<int S>() -> int {
+        return dispatch_dtype(dtype, [&]<typename T>() -> int {
+            constexpr int L = 16 / (int)sizeof(T);
+            return vec ? f.template operator()<S, T, L>() : f.template operator()<S, T, 1>();
+        });
+    });
+}
+// f.template operator()<M>() for the m in Ms that equals the run-time one; `what` is the error text when there is none.  The sets
+// ARE the instantiated kernels: M = 16 exists for the marching kernels only, M = 0 (more than 8 frames, run as time windows of
+// 8) for the one-sweep, one-pass and streaming kernels only.
+using MarchMs = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 16>;
+using WindowedMs = std::integer_sequence<int, 0, 1, 2, 3, 4, 5, 6, 7, 8>;
+template <int... Ms, typename F> inline int dispatch_m(std::integer_sequence<int, Ms...>, int m, const char* what, F&& f) {
+    int rc = 0;
+    const bool hit = ((m == Ms && ((rc = f.template operator()<Ms>()), true)) || ...);
+    return hit ? rc : fail(TV_E_ARG, what);
+}
+template <typename Ms, typename F> inline int dispatch_scheme_m(Ms ms, int scheme, int m, const char* what, F&& f) {
+    return dispatch_scheme(scheme, [&]<int S>() -> int {
+        return dispatch_m(ms, m, what, [&]<int M>() -> int { return f.template operator()<S, M>(); });
+    });
 }
 
 // ---- plane-marching fast path (tv_march.h): fp32, 16-byte lanes, M in {1,2,3,4,8,16} ---------------
@@ -194,16 +244,22 @@ inline int env_int(const char* name, int dflt) {
     const TvOption* o = find_option(name);
     return (o && o->has.load(std::memory_order_relaxed)) ? o->value.load(std::memory_order_relaxed) : dflt;
 }
-inline bool march_ok(const tv_geom* g, const DG& d, bool vec) {
-    if (g->dtype != TV_F32 || !vec || d.nx < 128) return false;
+// is a plane (M frames of `elt`-byte elements) big enough for the plane-marching / streaming kernels?  Small planes (z / t
+// neighbours one plane away stay L2-resident) are served better by the one-site-per-thread kernels: measured on 512x512xM=1
+// (BASELINE config 1)
+inline bool plane_big_enough(const DG& d, int elt) {
+    return (long long)d.s_z * elt >= (long long)env_int("TV_MARCH_MIN_PLANE_KB", 4096) * 1024;
+}
+// the geometry rule of the marching kernels, for elements of `elt` bytes
+inline bool march_geom_ok(const DG& d, bool vec, int elt) {
+    if (!vec || d.nx < 128) return false;
     if (d.wv != nullptr) return false;                    // weight volume: one-site-per-thread kernels
     if (d.pitched) return false;                          // pitched arrays (interface version 4): streaming / one-sweep / one-site kernels
     if (env_int("TV_NO_MARCH", 0)) return false;
-    // small planes (z/t neighbours one plane away stay L2-resident) are served better by the
-    // one-site-per-thread kernels: measured on 512x512xM=1 (BASELINE config 1)
-    if ((long long)d.s_z * 4 < (long long)env_int("TV_MARCH_MIN_PLANE_KB", 4096) * 1024) return false;
+    if (!plane_big_enough(d, elt)) return false;
     return (d.m >= 1 && d.m <= 8) || d.m == 16;
 }
+inline bool march_ok(const tv_geom* g, const DG& d, bool vec) { return g->dtype == TV_F32 && march_geom_ok(d, vec, 4); }
 // the marching ADJOINT (k_DT_march) is instantiated for double as well (round 4): the same rule with the plane measured in bytes -- for the
 // case where it wins: hybrid with a plain store (tv_DT, 32x8x1024x1024 fp64: 3.6 - 3.8 ms = 0.64 - 0.68 against 4.4 - 4.5 one-site; the Nd = 4
 // schemes are 10 - 20 % SLOWER marching, tv_DT_axpy is the same either way: profiles/r4_op_rooflines_f64_dt.txt)
@@ -211,10 +267,7 @@ inline bool march_dt_ok(const tv_geom* g, const DG& d, bool vec, bool plain_stor
     // fp32: everything but the plain adjoint of the one-sided schemes, where the one-site kernel is 3 - 5 % ahead (64x8x1024x1024: upwind 2.16 - 2.18
     // against 2.23 - 2.31 ms, downwind 2.15 - 2.19 against 2.30 - 2.39; hybrid 3.6 against 4.3 and central 2.4 - 2.5 against 2.75 the other way)
     if (g->dtype == TV_F32) return march_ok(g, d, vec) && !(plain_store && (g->scheme == TV_UPWIND || g->scheme == TV_DOWNWIND));
-    if (g->scheme != TV_HYBRID || !plain_store) return false;
-    if (!vec || d.nx < 128 || d.wv != nullptr || d.pitched || env_int("TV_NO_MARCH", 0)) return false;
-    if ((long long)d.s_z * 8 < (long long)env_int("TV_MARCH_MIN_PLANE_KB", 4096) * 1024) return false;
-    return (d.m >= 1 && d.m <= 8) || d.m == 16;
+    return g->scheme == TV_HYBRID && plain_store && march_geom_ok(d, vec, 8);        // fp64: march_ok's geometry rule at 8 bytes, for hybrid plain stores
 }
 inline int march_zchunk(const DG& d) {
     // planes per z-chunk: long chunks amortise the chunk prologue (and, for the one-sweep CP kernel, the
@@ -240,30 +293,21 @@ inline LC march_cfg(const DG& d, int zchunk) {
     lc.nblocks = tx * ty * nch;
     return lc;
 }
-template <typename F> inline int dispatch_sm(int scheme, int m, F&& f) {
-#define TV_CASE_M(SC)                                              \
-    case SC:                                                       \
-        switch (m) {                                               \
-            case 1: return f.template operator()<SC, 1>();         \
-            case 2: return f.template operator()<SC, 2>();         \
-            case 3: return f.template operator()<SC, 3>();         \
-            case 4: return f.template operator()<SC, 4>();         \
-            case 5: return f.template operator()<SC, 5>();         \
-            case 6: return f.template operator()<SC, 6>();         \
-            case 7: return f.template operator()<SC, 7>();         \
-            case 8: return f.template operator()<SC, 8>();         \
-            case 16: return f.template operator()<SC, 16>();       \
-        }                                                          \
-        break;
-    switch (scheme) { TV_CASE_M(0) TV_CASE_M(1) TV_CASE_M(2) TV_CASE_M(3) }
-#undef TV_CASE_M
-    return fail(TV_E_ARG, "unsupported (scheme, M) for the marching path");
-}
+inline constexpr const char* kNoMarchSM = "unsupported (scheme, M) for the marching path";
 inline int check_x_halos(const tv_geom* g, const DG& d, const void* xp, const void* xn) {
     if (!d.za) return 0;
     const bool need_prev = (g->scheme != TV_UPWIND), need_next = (g->scheme != TV_DOWNWIND);
     if (need_prev && g->z0 > 0 && xp == nullptr) return fail(TV_E_HALO, "previous-slab halo plane required");
     if (need_next && g->z0 + g->nz < g->nz_global && xn == nullptr) return fail(TV_E_HALO, "next-slab halo plane required");
+    return 0;
+}
+// the radius-2 evaluations from x alone (sub-gradient, normal operator): TWO planes of x on each interior side, whatever the scheme
+inline int check_x_halos2(const tv_geom* g, const DG& d, const void* x_prev, const void* x_next, const char* who) {
+    const bool e_lo = (g->z0 > 0), e_hi = (g->z0 + g->nz < g->nz_global);
+    if (d.za && ((e_lo && x_prev == nullptr) || (e_hi && x_next == nullptr))) {
+        g_err = std::string(who) + " on a slab needs two halo planes on each interior side";
+        return TV_E_HALO;
+    }
     return 0;
 }
 inline int check_y_halos(const tv_geom* g, const DG& d, const void* yp, const void* yn) {

@@ -642,6 +642,21 @@ __global__ __launch_bounds__(256) void k_reduce(const double* in, long long n, d
 
 }  // namespace tv
 
+// pass 2 of tv_subgrad with one site per thread: G from x and 1/|Dx| (norms_ext), V columns per lane
+template <int S, typename T, int V>
+static int launch_subgrad_vec(const tv_geom* g, const DG& d, const void* x, const void* x_prev, const void* x_next, const void* norms_ext,
+                              void* G, hipStream_t st) {
+    const LC lg = launch_cfg(d, V, d.nz);
+    if constexpr (S != CENTRAL)
+        hipLaunchKernelGGL((k_subgrad_vec<S, T, V>), lg.grid, lg.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev,
+                           (const T*)x_next, (const T*)norms_ext, (T*)G);
+    else
+        hipLaunchKernelGGL((k_subgrad_central_vec<T, V>), lg.grid, lg.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev,
+                           (const T*)x_next, (const T*)norms_ext, (T*)G);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 const char* tv_last_error(void) { return g_err.c_str(); }
@@ -672,7 +687,7 @@ int tv_num_channels(const tv_geom* g) {
 size_t tv_workspace_bytes(const tv_geom* g) {
     DG d;
     if (make_dg(g, d, true)) return 0;
-    return (size_t)(3 * (max_partials(d) + kStage + 16)) * sizeof(double);    // three independent partial arrays (the third: tv_cp_sweep with TV_CP_FID_BOTH, round 5)
+    return Partials::bytes(d);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -688,7 +703,7 @@ int tv_D(const tv_geom* g, const void* x, const void* x_prev, const void* x_next
     // (64x8x1024x1024, ms hybrid / upwind / downwind / central: k_D 4.90 / 2.39 / 2.37 / 3.04, k_D_march 5.76 / 2.71 /
     // 2.47 / 2.99, k_D_stream 4.31 / 2.16 / 2.17 / 2.31); on small planes the z / t neighbours of the one-site kernel
     // stay in L2 and it wins (256x1x512x512: 0.39 / 0.19 ms against 0.40 / 0.23) -- profiles/r2_d_kernels.txt
-    const bool big_plane = (long long)d.s_z * (g->dtype == TV_F32 ? 4 : 8) >= (long long)env_int("TV_MARCH_MIN_PLANE_KB", 4096) * 1024;
+    const bool big_plane = plane_big_enough(d, g->dtype == TV_F32 ? 4 : 8);
     const int kern = env_int("TV_D_KERNEL", env_int("TV_MARCH_D", 0) ? 1 : (big_plane ? 2 : 0));
     if (kern == 2 && tvm::D_stream_ok(g, d, vec) && !env_int("TV_NO_MARCH", 0))
         return tvm::D_stream(g, d, x, x_prev, x_next, st, dout);
@@ -761,12 +776,12 @@ int tv_l21(const tv_geom* g, const void* dimg, int32_t nd, void* norms, double* 
     d.s_dz = d.s_z * nd;
     const bool vec = rows_vectorisable(g, d) && aligned16({dimg, norms});
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     return dispatch(0, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lc = launch_cfg(d, V, d.nz);
-        hipLaunchKernelGGL((k_l21<T, V>), lc.grid, lc.block, 0, st, d, (const T*)dimg, (T*)norms, (double*)ws);
+        hipLaunchKernelGGL((k_l21<T, V>), lc.grid, lc.block, 0, st, d, (const T*)dimg, (T*)norms, P.slot(0));
         HIP_TRY(hipGetLastError());
-        return reduce_partials((double*)ws, lc.nblocks, nmax, result, st);
+        return P.reduce(0, lc.nblocks, result, st);
     });
 }
 
@@ -777,85 +792,44 @@ int tv_subgrad(const tv_geom* g, const void* x, const void* x_prev, const void* 
     if (int rc = make_dg(g, d, true)) return rc;
     if (x == nullptr || G == nullptr || norms_ext == nullptr || tvout == nullptr || ws == nullptr)
         return fail(TV_E_ARG, "NULL array");
+    if (int rc = check_x_halos2(g, d, x_prev, x_next, "tv_subgrad")) return rc;
     const int e_lo = (g->z0 > 0) ? 1 : 0, e_hi = (g->z0 + g->nz < g->nz_global) ? 1 : 0;
-    if (d.za && ((e_lo && x_prev == nullptr) || (e_hi && x_next == nullptr)))
-        return fail(TV_E_HALO, "tv_subgrad on a slab needs two halo planes on each interior side");
     if (d.za && d.ta && d.wv != nullptr && ((e_lo && d.wvp == nullptr) || (e_hi && d.wvn == nullptr)))
         return fail(TV_E_HALO, "tv_subgrad on a slab with a weight volume needs time_weight_prev / time_weight_next");
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, norms_ext, d.wv, d.wvp, d.wvn});
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
+    const int ghosts_lo = d.za ? e_lo : 0, ghosts_hi = d.za ? e_hi : 0;      // pass 1: norms on the local planes plus one ghost plane per interior side
     if (march_ok(g, d, vec && aligned16({G})) && !env_int("TV_NO_MARCH_SUBGRAD", 0)) {
         // plane-marching passes: every field is fetched once (tv_march.h / tv_fused.h)
-        const int glo = d.za ? e_lo : 0, ghi = d.za ? e_hi : 0;
         long long nb;
-        if (int rc = tvm::D_norms(g, d, x, x_prev, x_next, st, &nb, (float*)norms_ext, (double*)ws, glo, ghi)) return rc;
-        if (int rc = reduce_partials((double*)ws, nb, nmax, tvout, st)) return rc;
+        if (int rc = tvm::D_norms(g, d, x, x_prev, x_next, st, &nb, (float*)norms_ext, P.slot(0), ghosts_lo, ghosts_hi)) return rc;
+        if (int rc = P.reduce(0, nb, tvout, st)) return rc;
         if (tvm::subgrad_pass2_ok(g, d))
             return tvm::subgrad_pass2(g, d, x, x_prev, x_next, st, (const float*)norms_ext, (float*)G);
         // no marching gather for this case (central: radius-2 stencil; M > 8): one site per thread
-        LC lg = launch_cfg(d, 4, d.nz);
-        switch (g->scheme) {
-            case TV_UPWIND:
-                hipLaunchKernelGGL((k_subgrad_vec<UPWIND, float, 4>), lg.grid, lg.block, 0, st, d, make_w<float>(g), (const float*)x,
-                                   (const float*)x_prev, (const float*)x_next, (const float*)norms_ext, (float*)G);
-                break;
-            case TV_DOWNWIND:
-                hipLaunchKernelGGL((k_subgrad_vec<DOWNWIND, float, 4>), lg.grid, lg.block, 0, st, d, make_w<float>(g), (const float*)x,
-                                   (const float*)x_prev, (const float*)x_next, (const float*)norms_ext, (float*)G);
-                break;
-            case TV_HYBRID:
-                hipLaunchKernelGGL((k_subgrad_vec<HYBRID, float, 4>), lg.grid, lg.block, 0, st, d, make_w<float>(g), (const float*)x,
-                                   (const float*)x_prev, (const float*)x_next, (const float*)norms_ext, (float*)G);
-                break;
-            default:
-                hipLaunchKernelGGL((k_subgrad_central_vec<float, 4>), lg.grid, lg.block, 0, st, d, make_w<float>(g), (const float*)x,
-                                   (const float*)x_prev, (const float*)x_next, (const float*)norms_ext, (float*)G);
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return dispatch_scheme(g->scheme, [&]<int S>() -> int { return launch_subgrad_vec<S, float, 4>(g, d, x, x_prev, x_next, norms_ext, G, st); });
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        WT<T> w = make_w<T>(g);
-        // pass 1: norms on the local planes plus one ghost plane per interior side
-        const int ghosts_lo = d.za ? e_lo : 0, ghosts_hi = d.za ? e_hi : 0;
         LC lc = launch_cfg(d, V, d.nz + ghosts_lo + ghosts_hi);
-        NormEpi<S, T, V> epi{(T*)norms_ext, (double*)ws};
-        hipLaunchKernelGGL((k_D<S, T, V, NormEpi<S, T, V>>), lc.grid, lc.block, 0, st, d, w, (const T*)x, (const T*)x_prev,
+        NormEpi<S, T, V> epi{(T*)norms_ext, P.slot(0)};
+        hipLaunchKernelGGL((k_D<S, T, V, NormEpi<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev,
                            (const T*)x_next, 2, -ghosts_lo, epi);
         HIP_TRY(hipGetLastError());
-        if (int rc = reduce_partials((double*)ws, lc.nblocks, nmax, tvout, st)) return rc;
-        // pass 2: gather (vectorised for the radius-1 schemes, scalar radius-2 kernel for central)
-        if constexpr (S != CENTRAL) {
-            const bool v2 = vec && aligned16({G});
-            if (v2 && V > 1) {
-                LC lg = launch_cfg(d, V, d.nz);
-                hipLaunchKernelGGL((k_subgrad_vec<S, T, V>), lg.grid, lg.block, 0, st, d, w, (const T*)x, (const T*)x_prev,
-                                   (const T*)x_next, (const T*)norms_ext, (T*)G);
-            } else {
+        if (int rc = P.reduce(0, lc.nblocks, tvout, st)) return rc;
+        // pass 2: gather (vectorised; TV_SCALAR_GATHER: the reference-style scalar evaluation of central's radius-2 stencil, kept as an
+        // in-library cross-check)
+        if constexpr (S == CENTRAL) {
+            if (env_int("TV_SCALAR_GATHER", 0)) {
                 LC lg = launch_cfg(d, 1, d.nz);
-                hipLaunchKernelGGL((k_subgrad_vec<S, T, 1>), lg.grid, lg.block, 0, st, d, w, (const T*)x, (const T*)x_prev,
-                                   (const T*)x_next, (const T*)norms_ext, (T*)G);
-            }
-        } else if (env_int("TV_SCALAR_GATHER", 0)) {
-            // reference-style scalar evaluation of the radius-2 stencil (kept as an in-library cross-check)
-            LC lg = launch_cfg(d, 1, d.nz);
-            XA<T> X{d, (const T*)x, (const T*)x_prev, (const T*)x_next, 2};
-            hipLaunchKernelGGL((k_gather<S, T, 0>), lg.grid, lg.block, 0, st, X, w, (const T*)norms_ext, T(0), (T*)G, (double*)nullptr);
-        } else {
-            const bool v2 = vec && aligned16({G});
-            if (v2 && V > 1) {
-                LC lg = launch_cfg(d, V, d.nz);
-                hipLaunchKernelGGL((k_subgrad_central_vec<T, V>), lg.grid, lg.block, 0, st, d, w, (const T*)x, (const T*)x_prev,
-                                   (const T*)x_next, (const T*)norms_ext, (T*)G);
-            } else {
-                LC lg = launch_cfg(d, 1, d.nz);
-                hipLaunchKernelGGL((k_subgrad_central_vec<T, 1>), lg.grid, lg.block, 0, st, d, w, (const T*)x, (const T*)x_prev,
-                                   (const T*)x_next, (const T*)norms_ext, (T*)G);
+                XA<T> X{d, (const T*)x, (const T*)x_prev, (const T*)x_next, 2};
+                hipLaunchKernelGGL((k_gather<S, T, 0>), lg.grid, lg.block, 0, st, X, make_w<T>(g), (const T*)norms_ext, T(0), (T*)G, (double*)nullptr);
+                HIP_TRY(hipGetLastError());
+                return 0;
             }
         }
-        HIP_TRY(hipGetLastError());
-        return 0;
+        if (V > 1 && vec && aligned16({G})) return launch_subgrad_vec<S, T, V>(g, d, x, x_prev, x_next, norms_ext, G, st);
+        return launch_subgrad_vec<S, T, 1>(g, d, x, x_prev, x_next, norms_ext, G, st);
     });
 }
 
@@ -864,45 +838,41 @@ int tv_normal_op(const tv_geom* g, const void* x, const void* x_prev, const void
     DG d;
     if (int rc = make_dg(g, d, true)) return rc;
     if (x == nullptr || out == nullptr || dot == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
-    const int e_lo = (g->z0 > 0) ? 1 : 0, e_hi = (g->z0 + g->nz < g->nz_global) ? 1 : 0;
-    if (d.za && ((e_lo && x_prev == nullptr) || (e_hi && x_next == nullptr)))
-        return fail(TV_E_HALO, "tv_normal_op on a slab needs two halo planes on each interior side");
+    if (int rc = check_x_halos2(g, d, x_prev, x_next, "tv_normal_op")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, out, d.wv});
     // TV_NORMAL_KERNEL: 2 = streaming (k_normal_stream: default for fp32 planes >= TV_MARCH_MIN_PLANE_KB, radius-1 schemes,
     // any M), 1 = the marching LIGHT kernel of round 1 (M <= 8), 0 = one site per thread
     const int nkern = env_int("TV_NORMAL_KERNEL", 2);
     if (nkern == 2 && tvm::N_stream_ok(g, d, vec)) {
         long long nb;
-        double* w0 = (double*)ws;
-        double* w1 = w0 + nmax + kStage + 16;
-        if (int rc = tvm::N_stream(g, d, x, x_prev, x_next, nullptr, out, nullptr, rho, st, &nb, w0, w1)) return rc;
-        return reduce_partials(w0, nb, nmax, dot, st);
+        if (int rc = tvm::N_stream(g, d, x, x_prev, x_next, nullptr, out, nullptr, rho, st, &nb, P.slot(0), P.slot(1))) return rc;
+        return P.reduce(0, nb, dot, st);
     }
     if (nkern >= 1 && g->scheme != TV_CENTRAL && d.m <= 8 && march_ok(g, d, vec) && !env_int("TV_NO_MARCH_NORMAL", 0)) {
         long long nb;
-        if (int rc = tvm::D_normal_op(g, d, x, x_prev, x_next, st, &nb, (float*)out, (float)rho, (double*)ws)) return rc;
-        return reduce_partials((double*)ws, nb, nmax, dot, st);
+        if (int rc = tvm::D_normal_op(g, d, x, x_prev, x_next, st, &nb, (float*)out, (float)rho, P.slot(0))) return rc;
+        return P.reduce(0, nb, dot, st);
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lg = launch_cfg(d, V, d.nz);
         if constexpr (S != CENTRAL) {
             hipLaunchKernelGGL((k_normal_vec<S, T, V>), lg.grid, lg.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev,
-                               (const T*)x_next, (T)rho, (T*)out, (double*)ws);
+                               (const T*)x_next, (T)rho, (T*)out, P.slot(0));
         } else if (env_int("TV_SCALAR_GATHER", 0)) {
             LC l1 = launch_cfg(d, 1, d.nz);
             XA<T> X{d, (const T*)x, (const T*)x_prev, (const T*)x_next, 2};
             hipLaunchKernelGGL((k_gather<S, T, 1>), l1.grid, l1.block, 0, st, X, make_w<T>(g), (const T*)nullptr, (T)rho, (T*)out,
-                               (double*)ws);
+                               P.slot(0));
             HIP_TRY(hipGetLastError());
-            return reduce_partials((double*)ws, l1.nblocks, nmax, dot, st);
+            return P.reduce(0, l1.nblocks, dot, st);
         } else {
             hipLaunchKernelGGL((k_normal_central_vec<T, V>), lg.grid, lg.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev,
-                               (const T*)x_next, (T)rho, (T*)out, (double*)ws);
+                               (const T*)x_next, (T)rho, (T*)out, P.slot(0));
         }
         HIP_TRY(hipGetLastError());
-        return reduce_partials((double*)ws, lg.nblocks, nmax, dot, st);
+        return P.reduce(0, lg.nblocks, dot, st);
     });
 }
 
@@ -916,20 +886,19 @@ int tv_cp_dual(const tv_geom* g, const void* x, const void* x_prev, const void* 
     if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, d.wv});
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     if (march_ok(g, d, vec)) {
         long long nb;
-        if (int rc = tvm::D_cp_dual(g, d, x, x_prev, x_next, st, &nb, (float*)q, (float)sigma_D, (float)(1.0 / lambda),
-                                            (double*)ws)) return rc;
-        return reduce_partials((double*)ws, nb, nmax, tvout, st);
+        if (int rc = tvm::D_cp_dual(g, d, x, x_prev, x_next, st, &nb, (float*)q, (float)sigma_D, (float)(1.0 / lambda), P.slot(0))) return rc;
+        return P.reduce(0, nb, tvout, st);
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lc = launch_cfg(d, V, d.nz);
-        CpDual<S, T, V> epi{(T*)q, (T)sigma_D, (T)(1.0 / lambda), (double*)ws};
+        CpDual<S, T, V> epi{(T*)q, (T)sigma_D, (T)(1.0 / lambda), P.slot(0)};
         hipLaunchKernelGGL((k_D<S, T, V, CpDual<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
                            (const T*)x_prev, (const T*)x_next, 1, 0, epi);
         HIP_TRY(hipGetLastError());
-        return reduce_partials((double*)ws, lc.nblocks, nmax, tvout, st);
+        return P.reduce(0, lc.nblocks, tvout, st);
     });
 }
 
@@ -942,20 +911,20 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
     if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x0, p, d.wv});
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     if (march_ok(g, d, vec)) {
         long long nb;
         if (int rc = tvm::DT_cp_primal(g, d, q, q_prev, q_next, st, &nb, (float*)x, (const float*)x0, (float*)p, (float)tau,
-                                               (float)sigma_A, (float)(1.0 / (1.0 + sigma_A)), (double*)ws)) return rc;
-        return reduce_partials((double*)ws, nb, nmax, fid, st);
+                                               (float)sigma_A, (float)(1.0 / (1.0 + sigma_A)), P.slot(0))) return rc;
+        return P.reduce(0, nb, fid, st);
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lc = launch_cfg(d, V, d.nz);
         SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
-        CpPrimal<T, V> epi{(T*)x, (const T*)x0, (T*)p, (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), (double*)ws};
+        CpPrimal<T, V> epi{(T*)x, (const T*)x0, (T*)p, (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), P.slot(0)};
         hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimal<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
         HIP_TRY(hipGetLastError());
-        return reduce_partials((double*)ws, lc.nblocks, nmax, fid, st);
+        return P.reduce(0, lc.nblocks, fid, st);
     });
 }
 
@@ -971,44 +940,33 @@ int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void*
     if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, q_prev, q_next, x0, d.wv});
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
-    double* const w0 = (double*)ws;                       // |D x|_{2,1}
-    double* const w1 = w0 + nmax + kStage + 16;           // 1/2 |x - x0|^2
-    double* const w2 = w1 + nmax + kStage + 16;           // the gap
+    const Partials P(ws, d);                              // slot 0: |D x|_{2,1}, slot 1: 1/2 |x - x0|^2, slot 2: the gap
+    auto reduce3 = [&](long long n) -> int {
+        for (int k = 0; k < 3; ++k)
+            if (int rc = P.reduce(k, n, out + k, st)) return rc;
+        return 0;
+    };
     if (march_ok(g, d, vec) && d.m <= 8) {
         // plane-marching form, two launches on the same grid: q is read by both (2 Nd + 5 words per voxel).  Not M = 16: the D-side
         // kernel keeps 16 frames and their q samples in flight and spills (288 - 1540 bytes of scratch per lane)
         long long nb_dt, nb;
-        if (int rc = tvm::DT_gap(g, d, q, q_prev, q_next, st, &nb_dt, (const float*)x, (const float*)x0, (float)qscale, w2)) return rc;
-        if (int rc = tvm::D_gap(g, d, x, x_prev, x_next, st, &nb, (const float*)q, (const float*)x0, (float)qscale, lambda, w0, w1, w2))
+        if (int rc = tvm::DT_gap(g, d, q, q_prev, q_next, st, &nb_dt, (const float*)x, (const float*)x0, (float)qscale, P.slot(2))) return rc;
+        if (int rc = tvm::D_gap(g, d, x, x_prev, x_next, st, &nb, (const float*)q, (const float*)x0, (float)qscale, lambda, P.slot(0), P.slot(1),
+                                  P.slot(2)))
             return rc;
         if (nb != nb_dt) return fail(TV_E_ARG, "tv_dual_gap: the two marching passes disagree about the grid");
-        if (int rc = reduce_partials(w0, nb, nmax, out, st)) return rc;
-        if (int rc = reduce_partials(w1, nb, nmax, out + 1, st)) return rc;
-        return reduce_partials(w2, nb, nmax, out + 2, st);
+        return reduce3(nb);
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lc = launch_cfg(d, V, d.nz);
         SrcScaled<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next, (T)qscale};
         hipLaunchKernelGGL((k_gap<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
-                           src, (const T*)x0, lambda, w0, w1, w2);
+                           src, (const T*)x0, lambda, P.slot(0), P.slot(1), P.slot(2));
         HIP_TRY(hipGetLastError());
-        if (int rc = reduce_partials(w0, lc.nblocks, nmax, out, st)) return rc;
-        if (int rc = reduce_partials(w1, lc.nblocks, nmax, out + 1, st)) return rc;
-        return reduce_partials(w2, lc.nblocks, nmax, out + 2, st);
+        return reduce3(lc.nblocks);
     });
 }
 
-static int admm_zu_impl(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* z, void* u,
-                        double thresh, double* tvout, void* ws, void* stream, int tform);
-int tv_admm_zu(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* z, void* u,
-               double thresh, double* tvout, void* ws, void* stream) {
-    return admm_zu_impl(g, x, x_prev, x_next, z, u, thresh, tvout, ws, stream, 0);
-}
-int tv_admm_tu(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* t, void* u,
-               double thresh, double* tvout, void* ws, void* stream) {
-    return admm_zu_impl(g, x, x_prev, x_next, t, u, thresh, tvout, ws, stream, 1);
-}
 static int admm_zu_impl(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* z, void* u,
                         double thresh, double* tvout, void* ws, void* stream, int tform) {
     DG d;
@@ -1017,21 +975,28 @@ static int admm_zu_impl(const tv_geom* g, const void* x, const void* x_prev, con
     if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, z, u, d.wv});
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     if (march_ok(g, d, vec)) {
         long long nb;
-        if (int rc = tvm::D_admm_zu(g, d, x, x_prev, x_next, st, &nb, (float*)z, (float*)u, (float)thresh, (double*)ws, tform))
-            return rc;
-        return reduce_partials((double*)ws, nb, nmax, tvout, st);
+        if (int rc = tvm::D_admm_zu(g, d, x, x_prev, x_next, st, &nb, (float*)z, (float*)u, (float)thresh, P.slot(0), tform)) return rc;
+        return P.reduce(0, nb, tvout, st);
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lc = launch_cfg(d, V, d.nz);
-        AdmmZU<S, T, V> epi{(T*)z, (T*)u, (T)thresh, (double*)ws, tform};
+        AdmmZU<S, T, V> epi{(T*)z, (T*)u, (T)thresh, P.slot(0), tform};
         hipLaunchKernelGGL((k_D<S, T, V, AdmmZU<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
                            (const T*)x_prev, (const T*)x_next, 1, 0, epi);
         HIP_TRY(hipGetLastError());
-        return reduce_partials((double*)ws, lc.nblocks, nmax, tvout, st);
+        return P.reduce(0, lc.nblocks, tvout, st);
     });
+}
+int tv_admm_zu(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* z, void* u,
+               double thresh, double* tvout, void* ws, void* stream) {
+    return admm_zu_impl(g, x, x_prev, x_next, z, u, thresh, tvout, ws, stream, 0);
+}
+int tv_admm_tu(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* t, void* u,
+               double thresh, double* tvout, void* ws, void* stream) {
+    return admm_zu_impl(g, x, x_prev, x_next, t, u, thresh, tvout, ws, stream, 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1093,9 +1058,10 @@ int tv_dot(const tv_geom* g, const void* a, const void* b, double* result, void*
     if (int rc = make_dg(g, d, true)) return rc;
     if (a == nullptr || b == nullptr || result == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
     hipStream_t st = (hipStream_t)stream;
-    TV_FLAT_LAUNCH(k_dot, g->dtype, nvox(d), ({a, b}), (const T*)a, (const T*)b, (double*)ws);
+    const Partials P(ws, d);
+    TV_FLAT_LAUNCH(k_dot, g->dtype, nvox(d), ({a, b}), (const T*)a, (const T*)b, P.slot(0));
     HIP_TRY(hipGetLastError());
-    return reduce_partials((double*)ws, kFlatBlocks, max_partials(d), result, st);
+    return P.reduce(0, kFlatBlocks, result, st);
 }
 
 int tv_cg_step1(const tv_geom* g, void* x, void* r, const void* dvec, const void* Ad, const double* rs, const double* dAd,
@@ -1104,9 +1070,10 @@ int tv_cg_step1(const tv_geom* g, void* x, void* r, const void* dvec, const void
     if (int rc = make_dg(g, d, true)) return rc;
     if (!x || !r || !dvec || !Ad || !rs || !dAd || !rs_new || !ws) return fail(TV_E_ARG, "NULL array");
     hipStream_t st = (hipStream_t)stream;
-    TV_FLAT_LAUNCH(k_cg1, g->dtype, nvox(d), ({x, r, dvec, Ad}), (T*)x, (T*)r, (const T*)dvec, (const T*)Ad, rs, dAd, (double*)ws);
+    const Partials P(ws, d);
+    TV_FLAT_LAUNCH(k_cg1, g->dtype, nvox(d), ({x, r, dvec, Ad}), (T*)x, (T*)r, (const T*)dvec, (const T*)Ad, rs, dAd, P.slot(0));
     HIP_TRY(hipGetLastError());
-    return reduce_partials((double*)ws, kFlatBlocks, max_partials(d), rs_new, st);
+    return P.reduce(0, kFlatBlocks, rs_new, st);
 }
 
 int tv_cg_step2(const tv_geom* g, void* dvec, const void* r, const double* rs_new, const double* rs, void* stream) {
@@ -1125,9 +1092,10 @@ int tv_subgrad_step(const tv_geom* g, void* x, const void* x0, const void* G, do
     if (int rc = make_dg(g, d, true)) return rc;
     if (!x || !x0 || !G || !fid || !ws) return fail(TV_E_ARG, "NULL array");
     hipStream_t st = (hipStream_t)stream;
-    TV_FLAT_LAUNCH(k_sgstep, g->dtype, nvox(d), ({x, x0, G}), (T*)x, (const T*)x0, (const T*)G, (T)step, (T)lambda, (double*)ws);
+    const Partials P(ws, d);
+    TV_FLAT_LAUNCH(k_sgstep, g->dtype, nvox(d), ({x, x0, G}), (T*)x, (const T*)x0, (const T*)G, (T)step, (T)lambda, P.slot(0));
     HIP_TRY(hipGetLastError());
-    return reduce_partials((double*)ws, kFlatBlocks, max_partials(d), fid, st);
+    return P.reduce(0, kFlatBlocks, fid, st);
 }
 
 // out = A x (b == NULL) or out = b - A x (b != NULL; out2, when given, receives the same vector), A = I + rho D^T D;
@@ -1138,27 +1106,23 @@ int tv_normal_op2(const tv_geom* g, const void* x, const void* x_prev, const voi
     if (int rc = make_dg(g, d, true)) return rc;
     if (x == nullptr || out == nullptr || dots == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
     if (out2 != nullptr && b == nullptr) return fail(TV_E_ARG, "out2 is the copy of the residual: it needs b");
-    const int e_lo = (g->z0 > 0) ? 1 : 0, e_hi = (g->z0 + g->nz < g->nz_global) ? 1 : 0;
-    if (d.za && ((e_lo && x_prev == nullptr) || (e_hi && x_next == nullptr)))
-        return fail(TV_E_HALO, "tv_normal_op2 on a slab needs two halo planes on each interior side");
+    if (int rc = check_x_halos2(g, d, x_prev, x_next, "tv_normal_op2")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, out, out2, b, d.wv});
     if (env_int("TV_NORMAL_KERNEL", 2) == 2 && tvm::N_stream_ok(g, d, vec)) {
         long long nb;
-        double* w0 = (double*)ws;
-        double* w1 = w0 + nmax + kStage + 16;
-        if (int rc = tvm::N_stream(g, d, x, x_prev, x_next, b, out, out2, rho, st, &nb, w0, w1)) return rc;
-        if (int rc = reduce_partials(w0, nb, nmax, dots, st)) return rc;
-        return reduce_partials(w1, nb, nmax, dots + 1, st);
+        if (int rc = tvm::N_stream(g, d, x, x_prev, x_next, b, out, out2, rho, st, &nb, P.slot(0), P.slot(1))) return rc;
+        if (int rc = P.reduce(0, nb, dots, st)) return rc;
+        return P.reduce(1, nb, dots + 1, st);
     }
     // composition of the existing entry points (fp64, central, weight volume, small planes)
     if (int rc = tv_normal_op(g, x, x_prev, x_next, rho, out, dots, ws, stream)) return rc;
     if (int rc = tv_dot(g, x, x, dots + 1, ws, stream)) return rc;
     if (b != nullptr) {
-        TV_FLAT_LAUNCH(k_sub_dot, g->dtype, nvox(d), ({b, out, out2}), (const T*)b, (const T*)out, (T*)out, (T*)out2, (double*)ws);
+        TV_FLAT_LAUNCH(k_sub_dot, g->dtype, nvox(d), ({b, out, out2}), (const T*)b, (const T*)out, (T*)out, (T*)out2, P.slot(0));
         HIP_TRY(hipGetLastError());
-        return reduce_partials((double*)ws, kFlatBlocks, nmax, dots, st);
+        return P.reduce(0, kFlatBlocks, dots, st);
     }
     return 0;
 }
@@ -1174,31 +1138,27 @@ int tv_cheb_step(const tv_geom* g, const void* x, const void* x_prev, const void
     if (ref != nullptr && dots == nullptr) return fail(TV_E_ARG, "ref without a place for |out - ref|^2");
     if (out == x || out == y || out == b || out == add || out == ref) return fail(TV_E_ARG, "out must not alias an input");
     if (y != nullptr && yscale != 0.0) return fail(TV_E_ARG, "yscale is the stand-in for a missing y (y = yscale * b)");
-    const int e_lo = (g->z0 > 0) ? 1 : 0, e_hi = (g->z0 + g->nz < g->nz_global) ? 1 : 0;
-    if (d.za && ((e_lo && x_prev == nullptr) || (e_hi && x_next == nullptr)))
-        return fail(TV_E_HALO, "tv_cheb_step on a slab needs two halo planes on each interior side");
+    if (int rc = check_x_halos2(g, d, x_prev, x_next, "tv_cheb_step")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, out, b, y, add, ref, d.wv});
-    double* w0 = (double*)ws;
-    double* w1 = w0 + nmax + kStage + 16;
     if (env_int("TV_NORMAL_KERNEL", 2) == 2 && tvm::N_stream_ok(g, d, vec)) {
         long long nb;
         const tvm::NCheb c{y, add, ref, alpha, beta, yscale};
-        if (int rc = tvm::N_stream(g, d, x, x_prev, x_next, b, out, nullptr, rho, st, &nb, dots ? w0 : nullptr, dots ? w1 : nullptr, &c)) return rc;
+        if (int rc = tvm::N_stream(g, d, x, x_prev, x_next, b, out, nullptr, rho, st, &nb, dots ? P.slot(0) : nullptr, dots ? P.slot(1) : nullptr, &c))
+            return rc;
         if (dots == nullptr) return 0;
-        if (int rc = reduce_partials(w0, nb, nmax, dots, st)) return rc;
-        return reduce_partials(w1, nb, nmax, dots + 1, st);
+        if (int rc = P.reduce(0, nb, dots, st)) return rc;
+        return P.reduce(1, nb, dots + 1, st);
     }
     // composition: out <- A x with the operator of this geometry, then one flat pass
-    double* const scratch_dots = w1 + nmax + kStage + 16;        // dots == NULL: the partial sums still exist on this path, their totals go nowhere
-    if (dots == nullptr) dots = scratch_dots;
+    if (dots == nullptr) dots = P.spare(2);        // the partial sums still exist on this path, their two totals go nowhere
     if (int rc = tv_normal_op(g, x, x_prev, x_next, rho, out, dots, ws, stream)) return rc;
     TV_FLAT_LAUNCH(k_cheb_combine, g->dtype, nvox(d), ({x, b, y, add, ref, out}), (const T*)x, (const T*)b, (const T*)y, (const T*)add,
-                   (const T*)ref, (T*)out, (T)alpha, (T)beta, (T)yscale, w0, w1);
+                   (const T*)ref, (T*)out, (T)alpha, (T)beta, (T)yscale, P.slot(0), P.slot(1));
     HIP_TRY(hipGetLastError());
-    if (int rc = reduce_partials(w0, kFlatBlocks, nmax, dots, st)) return rc;
-    return reduce_partials(w1, kFlatBlocks, nmax, dots + 1, st);
+    if (int rc = P.reduce(0, kFlatBlocks, dots, st)) return rc;
+    return P.reduce(1, kFlatBlocks, dots + 1, st);
 }
 
 // out = a x + b y (y == NULL: out = a x); *dist2 (or NULL) = |out - ref|^2; out == NULL (with ref): the distance alone, nothing stored
@@ -1209,9 +1169,10 @@ int tv_axpby(const tv_geom* g, double a, const void* x, double b, const void* y,
     if (x == nullptr || (out == nullptr && ref == nullptr)) return fail(TV_E_ARG, "NULL array");
     if ((ref != nullptr) != (dist2 != nullptr) || (ref != nullptr && ws == nullptr)) return fail(TV_E_ARG, "ref, dist2 and ws go together");
     hipStream_t st = (hipStream_t)stream;
-    TV_FLAT_LAUNCH(k_axpby, g->dtype, nvox(d), ({x, y, ref, out}), (T)a, (const T*)x, (T)b, (const T*)y, (const T*)ref, (T*)out, (double*)ws);
+    const Partials P(ws, d);
+    TV_FLAT_LAUNCH(k_axpby, g->dtype, nvox(d), ({x, y, ref, out}), (T)a, (const T*)x, (T)b, (const T*)y, (const T*)ref, (T*)out, P.slot(0));
     HIP_TRY(hipGetLastError());
-    if (ref != nullptr) return reduce_partials((double*)ws, kFlatBlocks, max_partials(d), dist2, st);
+    if (ref != nullptr) return P.reduce(0, kFlatBlocks, dist2, st);
     return 0;
 }
 
@@ -1223,11 +1184,12 @@ int tv_cg_update(const tv_geom* g, void* x, void* r, void* dvec, void* s, const 
     if (!x || !r || !dvec || !s || !w || !sc || !ws) return fail(TV_E_ARG, "NULL array");
     if (x0 != nullptr && fid == nullptr) return fail(TV_E_ARG, "x0 without a place for the fidelity");
     hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
     TV_FLAT_LAUNCH(k_cgcg, g->dtype, nvox(d), ({x, r, dvec, s, w, x0}), (T*)x, (T*)r, (T*)dvec, (T*)s, (const T*)w, (const double*)sc,
-                   (const T*)x0, (double*)ws);
+                   (const T*)x0, P.slot(0));
     hipLaunchKernelGGL(k_cgcg_advance, dim3(1), dim3(1), 0, st, sc);
     HIP_TRY(hipGetLastError());
-    if (x0 != nullptr) return reduce_partials((double*)ws, kFlatBlocks, max_partials(d), fid, st);
+    if (x0 != nullptr) return P.reduce(0, kFlatBlocks, fid, st);
     return 0;
 }
 

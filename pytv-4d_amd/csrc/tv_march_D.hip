@@ -9,7 +9,7 @@ static int launch_D_march(const tv_geom* g, const DG& d, const void* x, const vo
     const int zc = march_zchunk(d);
     const LC lc = march_cfg(d, zc);
     *nblocks = lc.nblocks;
-    return dispatch_sm(g->scheme, d.m, [&]<int S, int M>() -> int {
+    return dispatch_scheme_m(MarchMs{}, g->scheme, d.m, kNoMarchSM, [&]<int S, int M>() -> int {
         EpiT<S, float, 4> epi{args...};
         hipLaunchKernelGGL((k_D_march<S, M, EpiT<S, float, 4>>), lc.grid, lc.block, 0, st, d, make_w<float>(g), (const float*)x,
                            (const float*)xp, (const float*)xn, zc, epi);
@@ -42,7 +42,7 @@ int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const 
     lc.grid.y = (unsigned)((planes + zc - 1) / zc);
     lc.nblocks = (long long)lc.grid.x * lc.grid.y;
     *nb = lc.nblocks;
-    return dispatch_sm(g->scheme, d.m, [&]<int S, int M>() -> int {
+    return dispatch_scheme_m(MarchMs{}, g->scheme, d.m, kNoMarchSM, [&]<int S, int M>() -> int {
         NormEpi<S, float, 4> epi{norms_ext, partials};
         // low-traffic epilogue: M = 8 requests the whole next plane and the halo rows at the top of the z step
         // (PF = 2, 2 waves/SIMD); smaller M take the LIGHT variant (3 waves/SIMD, single-buffered tile), 15-20 %
@@ -67,15 +67,15 @@ int D_normal_op(const tv_geom* g, const DG& d, const void* x, const void* xp, co
     *nb = lc.nblocks;
     const WT<float> w = make_w<float>(g);
     NormalEpi<HYBRID, float, 4> epi{out, rho, w.wz, w.wt, w.sf, d.mask, partials};
-    return dispatch_sm(TV_HYBRID, d.m, [&]<int S, int M>() -> int {
-        if constexpr (S == HYBRID && M == 8) {
+    return dispatch_m(MarchMs{}, d.m, kNoMarchSM, [&]<int M>() -> int {
+        if constexpr (M == 8) {
             // whole next plane + halo rows requested at the top of the z step: 1.61 -> 1.28 ms on 64x8x1024x1024
             hipLaunchKernelGGL((k_D_march<HYBRID, M, NormalEpi<HYBRID, float, 4>, false, 2>), lc.grid, lc.block, 0, st, d, w,
                                (const float*)x, (const float*)xp, (const float*)xn, zc, epi, 2, 0, -1);
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if constexpr (S == HYBRID && M <= 8) {
+        if constexpr (M <= 8) {          // (M == 8 returned above; its instantiation of this form stays part of the library)
             hipLaunchKernelGGL((k_D_march<HYBRID, M, NormalEpi<HYBRID, float, 4>, true>), lc.grid, lc.block, 0, st, d, w,
                                (const float*)x, (const float*)xp, (const float*)xn, zc, epi, 2, 0, -1);
             HIP_TRY(hipGetLastError());

@@ -10,7 +10,7 @@ static int launch_DT_march(const tv_geom* g, const DG& d, const void* q, const v
     const int zc = march_zchunk(d);
     const LC lc = march_cfg(d, zc);
     *nblocks = lc.nblocks;
-    return dispatch_sm(g->scheme, d.m, [&]<int S, int M>() -> int {
+    return dispatch_scheme_m(MarchMs{}, g->scheme, d.m, kNoMarchSM, [&]<int S, int M>() -> int {
         EpiT<T, V> epi{args...};
         hipLaunchKernelGGL((k_DT_march<S, M, EpiT<T, V>, T>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)q,
                            (const T*)qp, (const T*)qn, zc, epi);

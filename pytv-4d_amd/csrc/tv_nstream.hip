@@ -13,11 +13,10 @@ bool N_stream_ok(const tv_geom* g, const DG& d, bool vec) {
     // per-element masks anyway); `vec` says the rows start on 16-byte boundaries
     if (!vec || d.nx < 64 || d.wv != nullptr) return false;
     if (g->scheme == TV_CENTRAL && ((d.za && d.z_two) || (d.ta && d.t_two))) return false;   // two-point axes: forward stencil
-    const long long eb = (g->dtype == TV_F32) ? 4 : 8;
+    const int eb = (g->dtype == TV_F32) ? 4 : 8;
     if (d.s_z * eb >= (1ll << 31)) return false;     // plane descriptors: num_records and the out-of-range offset (tv_fused.h, BUF_OOB)
     if (env_int("TV_NO_MARCH", 0) || env_int("TV_NO_MARCH_NORMAL", 0)) return false;
-    // small planes: the z / t neighbours of the one-site kernel stay in L2 (same threshold as the other streaming kernels)
-    return (long long)d.s_z * eb >= (long long)env_int("TV_MARCH_MIN_PLANE_KB", 4096) * 1024;
+    return plane_big_enough(d, eb);
 }
 
 int N_stream(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, const void* b, void* out, void* out2,
@@ -47,52 +46,38 @@ int N_stream(const tv_geom* g, const DG& d, const void* x, const void* xp, const
     const dim3 grid((unsigned)(8 * per_xcd), 1, 1), block(64, ST_NWX * ST_NWY, 1);
     *nblocks = 8 * per_xcd;
     if (*nblocks > max_partials(d)) return fail(TV_E_ARG, "internal: normal-operator partials exceed the workspace");
-    const WT<float> w = make_w<float>(g);
     const NCheb c0{nullptr, nullptr, nullptr, 0.0, 0.0, 0.0};
     const NCheb& c = cheb ? *cheb : c0;
-    NormalArgs a{(const float*)x, (const float*)xp, (const float*)xn, (const float*)b, (float*)out, (float*)out2, (float)rho, part0, part1,
-                 (const float*)c.y, (const float*)c.add, (const float*)c.ref, (float)c.alpha, (float)c.beta, cheb ? 1 : 0, (float)c.yscale};
-    NormalArgsT<double> ad{(const double*)x, (const double*)xp, (const double*)xn, (const double*)b, (double*)out, (double*)out2, rho, part0, part1,
-                           (const double*)c.y, (const double*)c.add, (const double*)c.ref, c.alpha, c.beta, cheb ? 1 : 0, c.yscale};
-#define TV_NS_LAUNCH1(MM, TW, CH)                                                                                       \
-    do {                                                                                                               \
-        if (g->scheme == TV_CENTRAL && TW && ragged) {                                                                 \
-            if (g->dtype == TV_F64) hipLaunchKernelGGL((k_normal_stream_cen<MM, TW, CH, double, TW>), grid, block, 0, st, d, make_w<double>(g), ad, zc, (int)nch); \
-            else hipLaunchKernelGGL((k_normal_stream_cen<MM, TW, CH, float, TW>), grid, block, 0, st, d, w, a, zc, (int)nch); \
-        }                                                                                                              \
-        else if (g->dtype == TV_F64 && g->scheme == TV_CENTRAL)                                                        \
-            hipLaunchKernelGGL((k_normal_stream_cen<MM, TW, CH, double>), grid, block, 0, st, d, make_w<double>(g), ad, zc, (int)nch); \
-        else if (g->scheme == TV_CENTRAL) hipLaunchKernelGGL((k_normal_stream_cen<MM, TW, CH, float>), grid, block, 0, st, d, w, a, zc, (int)nch); \
-        else if (TW && ragged) {          /* tv_nstream.h, RAGGED: the last window is short */                       \
-            if (g->dtype == TV_F64) hipLaunchKernelGGL((k_normal_stream<MM, TW, double, CH, TW>), grid, block, 0, st, d, make_w<double>(g), ad, zc, (int)nch); \
-            else hipLaunchKernelGGL((k_normal_stream<MM, TW, float, CH, TW>), grid, block, 0, st, d, w, a, zc, (int)nch); \
-        }                                                                                                              \
-        else if (g->dtype == TV_F64) hipLaunchKernelGGL((k_normal_stream<MM, TW, double, CH>), grid, block, 0, st, d, make_w<double>(g), ad, zc, (int)nch); \
-        else hipLaunchKernelGGL((k_normal_stream<MM, TW, float, CH>), grid, block, 0, st, d, w, a, zc, (int)nch);       \
-    } while (0)
-    // the Chebyshev epilogue is its own instantiation (tv_nstream.h, ns_epilogue), and so is the first step of a solve (no operand streams)
+    // the Chebyshev epilogue is its own instantiation (tv_nstream.h, ns_epilogue: CH = 1), and so is the first step of a solve (no operand
+    // streams: CH = 2)
     const bool cheb_first = cheb != nullptr && b == x && c.y == nullptr && c.add == nullptr && c.ref == nullptr && !env_int("TV_NS_NO_FIRST", 0);
-#define TV_NS_LAUNCH(MM, TW)                                                                                            \
-    do {                                                                                                               \
-        if (cheb_first) TV_NS_LAUNCH1(MM, TW, 2);                                                                      \
-        else if (cheb) TV_NS_LAUNCH1(MM, TW, 1);                                                                       \
-        else TV_NS_LAUNCH1(MM, TW, 0);                                                                                 \
-    } while (0)
-    switch (d.m > NS_TWN ? 0 : d.m) {
-        case 0: TV_NS_LAUNCH(NS_TWN, true); break;
-        case 1: TV_NS_LAUNCH(1, false); break;
-        case 2: TV_NS_LAUNCH(2, false); break;
-        case 3: TV_NS_LAUNCH(3, false); break;
-        case 4: TV_NS_LAUNCH(4, false); break;
-        case 5: TV_NS_LAUNCH(5, false); break;
-        case 6: TV_NS_LAUNCH(6, false); break;
-        case 7: TV_NS_LAUNCH(7, false); break;
-        default: TV_NS_LAUNCH(8, false); break;
-    }
-#undef TV_NS_LAUNCH
-#undef TV_NS_LAUNCH1
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const bool central = (g->scheme == TV_CENTRAL);
+    // every M <= 8 has its own instantiation; more frames (M == 0 here) run as time windows of NS_TWN frames, with a form of their own
+    // when the last window is short (tv_nstream.h, RAGGED)
+    return dispatch_m(WindowedMs{}, d.m > NS_TWN ? 0 : d.m, "unsupported M for the streaming normal operator", [&]<int M>() -> int {
+        return dispatch_dtype(g->dtype, [&]<typename T>() -> int {
+            constexpr bool TW = (M == 0);
+            constexpr int MM = TW ? NS_TWN : M;
+            const WT<T> w = make_w<T>(g);
+            const NormalArgsT<T> a{(const T*)x, (const T*)xp, (const T*)xn, (const T*)b, (T*)out, (T*)out2, (T)rho, part0, part1,
+                                   (const T*)c.y, (const T*)c.add, (const T*)c.ref, (T)c.alpha, (T)c.beta, cheb ? 1 : 0, (T)c.yscale};
+            auto launch = [&]<int CH, bool RAGGED>() {
+                if (central) hipLaunchKernelGGL((k_normal_stream_cen<MM, TW, CH, T, RAGGED>), grid, block, 0, st, d, w, a, zc, (int)nch);
+                else hipLaunchKernelGGL((k_normal_stream<MM, TW, T, CH, RAGGED>), grid, block, 0, st, d, w, a, zc, (int)nch);
+            };
+            auto launch_ch = [&]<int CH>() {
+                if constexpr (TW) {
+                    if (ragged) return launch.template operator()<CH, true>();
+                }
+                launch.template operator()<CH, false>();
+            };
+            if (cheb_first) launch_ch.template operator()<2>();
+            else if (cheb) launch_ch.template operator()<1>();
+            else launch_ch.template operator()<0>();
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+    });
 }
 
 }  // namespace tvm

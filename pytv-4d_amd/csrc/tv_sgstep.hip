@@ -10,7 +10,7 @@ int tv_subgrad_step_fused(const tv_geom* g, const void* x, const void* x_prev, c
     if (x == x_out) return fail(TV_E_ARG, "x and x_out must be different buffers (ping-pong)");
     SgHostArgs sa{x0, x_out, step, lambda, nullptr};
     return sg_launch<1>(g, x, x_prev, x_next, nullptr, tvout, fid, ws, stream, sa,
-                        "tv_subgrad_step_fused on a slab needs two halo planes on each interior side");
+                        "tv_subgrad_step_fused");
 }
 
 }  // extern "C"

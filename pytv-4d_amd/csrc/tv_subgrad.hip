@@ -9,7 +9,7 @@ int tv_subgrad_fused(const tv_geom* g, const void* x, const void* x_prev, const 
                      void* ws, void* stream) {
     if (G == nullptr) return fail(TV_E_ARG, "NULL array");
     return sg_launch<0>(g, x, x_prev, x_next, G, tvout, nullptr, ws, stream, SgHostArgs{},
-                        "tv_subgrad_fused on a slab needs two halo planes on each interior side");
+                        "tv_subgrad_fused");
 }
 
 }  // extern "C"

@@ -5,13 +5,9 @@
 #include "tv_stencil.h"
 #include "tv_subgrad2.h"
 
-// every M <= 8 has its own instantiation; more frames run as overlapping time windows of 8 frames (tv_subgrad.h)
-inline bool sg_m_ok(int m) { return m >= 1; }
-
 inline int sg_supported(const tv_geom* g) {
     DG d;
     if (make_dg(g, d, true)) return 0;
-    if (!sg_m_ok(d.m)) return 0;
     // the round-3 kernel holds ONE column per lane (4- / 8-byte buffer loads): any Nx, any element-aligned pointer (late round 3;
     // before, ragged Nx took the two-pass path at 0.11 - 0.17 of the roofline).  The round-1 kernel (TV_SG_KERNEL=1, frames of
     // 2^31 bytes and more) is fp32 with 16-byte lanes.
@@ -27,26 +23,6 @@ inline int sg_supported(const tv_geom* g) {
     if (d.m > SG2_TWN && env_int("TV_NO_FUSED_TWIN", 0)) return 0;
     if (env_int("TV_NO_FUSED_SUBGRAD", 0)) return 0;
     return 1;
-}
-
-template <typename F> inline int dispatch_sg(int scheme, int m, F&& f) {
-#define TV_CASE_G(SC)                                              \
-    case SC:                                                       \
-        switch (m) {                                               \
-            case 0: return f.template operator()<SC, 0>();         \
-            case 1: return f.template operator()<SC, 1>();         \
-            case 2: return f.template operator()<SC, 2>();         \
-            case 3: return f.template operator()<SC, 3>();         \
-            case 4: return f.template operator()<SC, 4>();         \
-            case 5: return f.template operator()<SC, 5>();         \
-            case 6: return f.template operator()<SC, 6>();         \
-            case 7: return f.template operator()<SC, 7>();         \
-            case 8: return f.template operator()<SC, 8>();         \
-        }                                                          \
-        break;
-    switch (scheme) { TV_CASE_G(0) TV_CASE_G(1) TV_CASE_G(2) TV_CASE_G(3) }
-#undef TV_CASE_G
-    return fail(TV_E_ARG, "unsupported (scheme, M) for the one-pass sub-gradient");
 }
 
 // what the C entry points hand to the launcher (dtype-neutral)
@@ -98,7 +74,7 @@ inline int sg2_launch(const tv_geom* g, const DG& d, const void* x, const void* 
     const bool al = TV_SG2_AL && al_scheme && d.m <= SG2_TWN && d.wv == nullptr && d.s_t * (long long)sizeof(T) * d.m < (1ll << 31) &&
                     (!F64 || MODE != 0);
     const int NW = al ? 8 : (F64 ? 4 : TV_SG2_NW32), NWX = (F64 || al) ? 1 : TV_SG2_NWX;
-    const long long nmax = max_partials(d);
+    const Partials P(ws, d);
     const bool halo = (g->scheme == TV_HYBRID || g->scheme == TV_CENTRAL);
     const int UR = R * NW - 2, UC = al ? 64 : (halo ? 60 : 62);
     const long long tx = (d.nx + UC - 1) / UC, ty = (d.ny + UR - 1) / UR;
@@ -140,14 +116,14 @@ inline int sg2_launch(const tv_geom* g, const DG& d, const void* x, const void* 
     tm.nfast = (long long)(ix1 - ix0 + 1) * (iy1 - iy0 + 1);
     tm.nborder = txb * ty - tm.nfast;
     const long long nbf = tm.nfast * nch * nwin, nbb = tm.nborder * nch * nwin, nb = nbf + nbb;
-    if (nb > nmax) return fail(TV_E_ARG, "internal: partials exceed the workspace");
+    if (nb > P.nmax) return fail(TV_E_ARG, "internal: partials exceed the workspace");
     const long long ngrid = (nbb + 7) / 8 * 8 + (nbf + 7) / 8 * 8;
     if (ngrid > 0x7fffffffll) return fail(TV_E_ARG, "volume too large for the one-pass sub-gradient grid");
     const dim3 block(64, NW * NWX, 1);
-    double* w0 = (double*)ws;
-    double* w1 = w0 + nmax + kStage + 16;
-    SgArgs2<T> sa{(const T*)so.x0, (T*)so.x_out, (T)so.step, (T)so.lambda, w1, (T*)so.norms};
-    int rc = dispatch_sg(g->scheme, d.m > SG2_TWN ? 0 : d.m, [&]<int S, int M>() -> int {
+    double* const w0 = P.slot(0);
+    SgArgs2<T> sa{(const T*)so.x0, (T*)so.x_out, (T)so.step, (T)so.lambda, P.slot(1), (T*)so.norms};
+    // every M <= 8 has its own instantiation; more frames (M == 0 here) run as overlapping time windows of 8 frames (tv_subgrad2.h)
+    int rc = dispatch_scheme_m(WindowedMs{}, g->scheme, d.m > SG2_TWN ? 0 : d.m, "unsupported (scheme, M) for the one-pass sub-gradient", [&]<int S, int M>() -> int {
         constexpr int MM = (M == 0) ? SG2_TWN : M;
         constexpr bool TW = (M == 0);
         if constexpr (!TW && (!F64 || MODE != 0) && (TV_SG2_AL == 2 || (TV_SG2_AL == 1 && (S == UPWIND || S == DOWNWIND)))) {
@@ -164,8 +140,8 @@ inline int sg2_launch(const tv_geom* g, const DG& d, const void* x, const void* 
         return 0;
     });
     if (rc) return rc;
-    if (int r2 = reduce_partials(w0, nb, nmax, tvout, st)) return r2;
-    if (MODE == 1) return reduce_partials(w1, nb, nmax, fidout, st);
+    if (int r2 = P.reduce(0, nb, tvout, st)) return r2;
+    if (MODE == 1) return P.reduce(1, nb, fidout, st);
     return 0;
 }
 
@@ -178,9 +154,7 @@ inline int sg_launch(const tv_geom* g, const void* x, const void* x_prev, const 
     if (int rc = make_dg(g, d, true)) return rc;      // pitched arrays: the round-3 kernel (one column per lane: pads are never touched)
     if (x == nullptr || tvout == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
     if (!sg_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-pass sub-gradient");
-    const bool vec16 = (d.nx % 4 == 0) && aligned16({x, x_prev, x_next, G, ha.x0, ha.x_out, ha.norms});      // what the round-1 kernel needs
-    const int e_lo = (g->z0 > 0) ? 1 : 0, e_hi = (g->z0 + g->nz < g->nz_global) ? 1 : 0;
-    if (d.za && ((e_lo && x_prev == nullptr) || (e_hi && x_next == nullptr))) return fail(TV_E_HALO, who);
+    if (int rc = check_x_halos2(g, d, x_prev, x_next, who)) return rc;
     hipStream_t st = (hipStream_t)stream;
     // round-3 kernel unless switched off; its descent step divides by step * lambda (tv_subgrad2.h): tiny or zero products
     // take the round-1 kernel; frames must stay below 2^31 bytes for its buffer addressing
@@ -193,6 +167,5 @@ inline int sg_launch(const tv_geom* g, const void* x, const void* x_prev, const 
         return sg2_launch<float, MODE>(g, d, x, x_prev, x_next, G, tvout, fidout, ws, st, ha);
     // the product library holds ONE generation of the one-pass kernel (round-4 verdict, item 7): what it cannot take goes to the two-pass
     // entry points (tv_subgrad + tv_subgrad_step), as solvers.SubgradientDescent does on its own
-    (void)vec16;
     return fail(TV_E_ARG, "the one-pass sub-gradient kernel needs step * lambda >= 1e-6 and frames below 2^31 bytes: use tv_subgrad + tv_subgrad_step");
 }

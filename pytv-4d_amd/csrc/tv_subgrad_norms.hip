@@ -11,7 +11,7 @@ int tv_subgrad_fused_norms(const tv_geom* g, const void* x, const void* x_prev, 
     SgHostArgs sa{};
     sa.norms = norms;
     return sg_launch<2>(g, x, x_prev, x_next, G, tvout, nullptr, ws, stream, sa,
-                        "tv_subgrad_fused_norms on a slab needs two halo planes on each interior side");
+                        "tv_subgrad_fused_norms");
 }
 
 }  // extern "C"

@@ -96,6 +96,13 @@ int main() {
             loss[variant][it] = h[1] + h[2] + lambda * h[0];
         }
         printf("%-22s loss: %.6e -> %.6e\n", variant == 0 ? "tv_cp_dual + primal" : "tv_cp_fused + fixup", loss[variant][0], loss[variant][4]);
+        if (variant == 0) {     // what the next dual update would still change (reduce-only: x and q are left alone)
+            double h[2] = {0, 0};
+            TV_OK(tv_cp_dual_residual(&g, xa, nullptr, nullptr, q, sigma_D, lambda, sc, ws, st));
+            HIP_OK(hipMemcpyAsync(h, sc, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            printf("%-22s |Dx|_{2,1} = %.6e, |q - proj(q + sigma D x)|^2 / sigma^2 = %.6e\n", "tv_cp_dual_residual", h[0], h[1]);
+        }
         for (float* b : {xa, xb, x0, p, q}) (void)hipFree(b);
         if (!(loss[variant][4] < loss[variant][0])) { fprintf(stderr, "loss did not decrease\n"); return 1; }
     }

@@ -198,6 +198,22 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
 int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
                 const void* q_next, const void* x0, double lambda, double qscale, double* out, void* ws, void* stream);
 
+/* Optimality residual of the TV block of the saddle problem Chambolle-Pock iterates on, for solvers whose fidelity term has no cheap dual
+ * objective (a general operator A: pytv.solvers.ChambollePockOperator).  (x, q) is stationary for that block iff q = proj(q + s D x) for one
+ * (equivalently every) s > 0; over the local planes
+ *   out[0] = |D x|_{2,1}
+ *   out[1] = sum_sites |q - proj_{|.|_2 <= lambda}(q + sigma_D D x)|_2^2 / sigma_D^2
+ * out[1] is accumulated site by site in that form, in fp64, never as a difference of two sums.  The update and the projection are the very
+ * arithmetic of tv_cp_dual (one shared device function, IEEE sqrt / divide): q - proj(..) is bit for bit what the next tv_cp_dual with the
+ * same sigma_D would change, and out[1] == 0 exactly where it would change nothing.
+ * REDUCE-ONLY: nothing is written except out (two device fp64 words) and ws.  x_prev / x_next as in tv_cp_dual; slab partials add up to the
+ * unsharded scalars.  lambda > 0 and a finite sigma_D > 0, else TV_E_ARG; a missing halo plane is TV_E_HALO; all checks precede any device
+ * access.  Every geometry tv_cp_dual takes (four schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays, weight maps / volumes,
+ * z-slabs): one launch of the one-site-per-thread kernel, Nd + 1 words per voxel.  Large planes stay on that kernel as well -- the call
+ * is made once per convergence check, not once per iteration. */
+int tv_cp_dual_residual(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, double sigma_D,
+                        double lambda, double* out, void* ws, void* stream);
+
 /* One-sweep form of the same iteration (all four schemes; fp32, nx % 4 == 0, nx >= 64,
  * any m: more than 8 frames are processed as time windows of 8): q is read and written ONCE per
  * iteration.  x is ping-ponged.

@@ -10,6 +10,7 @@
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
 //                StoreDT / AxpyDT / CpPrimal epilogues           (tv_DT, tv_DT_axpy, tv_cp_primal)
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
+//   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
 //   k_normal_vec  / k_normal_central_vec  : x + rho D^T D x from x alone   (tv_normal_op)
 //   k_gather : scalar reference evaluation of the last two (TV_SCALAR_GATHER=1)
@@ -94,6 +95,60 @@ __global__ __launch_bounds__(256) void k_gap(DG g, WT<T> w, const T* x, const T*
     if (first) p_fid[b] = fid;
     const double gap = block_sum(a[2], sm);
     if (first) p_gap[b] = gap;
+}
+
+// prox-gradient residual of the TV block of the Chambolle-Pock saddle problem, reduce-only (tv_cp_dual_residual): a thread runs the dual
+// update of its site with CpDual's own arithmetic (cp_dual_site) and, instead of storing the new q, sums (q - q_new)^2 over the site's
+// channels, divided by sigma^2 -- the site's term, never a difference of two sums.  Two sums per block: |D x|_2 and that term.
+// The product v * scale and the difference are rounded separately (no fused multiply-add): q_new is the value tv_cp_dual would store.
+template <typename T, int V>
+__device__ __forceinline__ double cp_change_sq(const Vec<T, V>& qo, const Vec<T, V>& v, const Vec<T, V>& scale) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        double e;
+        {
+#pragma clang fp contract(off)
+            const T qn = v.v[i] * scale.v[i];
+            e = (double)qo.v[i] - (double)qn;
+        }
+        s += e * e;
+    }
+    return s;
+}
+template <int S, typename T, int V> struct CpDualRes {
+    static constexpr bool REDUCES = true;
+    const T* q;
+    T sigma, inv_lambda;
+    double inv_sigma2;
+    double* acc2;        // the calling thread's two sums
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        const T* base = q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        Vec<T, V> v[8];
+        Vec<T, V> scale;
+        acc2[0] += cp_dual_site<S, T, V>(g, base, o, sigma, inv_lambda, v, scale);
+        double r = 0.0;
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            constexpr int k = decltype(slot)::value;
+            r += cp_change_sq<T, V>(vload_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z), v[k], scale);   // (the load cp_dual_site made)
+        });
+        acc2[1] += r * inv_sigma2;
+        return 0.0;
+    }
+};
+template <int S, typename T, int V>
+__global__ __launch_bounds__(256) void k_cp_res(DG g, WT<T> w, const T* x, const T* xp, const T* xn, const T* q, T sigma, T inv_lambda,
+                                                 double inv_sigma2, double* p_tv, double* p_res) {
+    __shared__ double sm[16];
+    const Coord c = thread_coord<V>(g, 0);
+    double a[2] = {0.0, 0.0};
+    d_site<S, T, V>(g, w, x, xp, xn, 1, c, CpDualRes<S, T, V>{q, sigma, inv_lambda, inv_sigma2, a}, PlainMem());
+    const long long b = linear_block_id();
+    const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
+    const double tv = block_sum(a[0], sm);
+    if (first) p_tv[b] = tv;
+    const double res = block_sum(a[1], sm);
+    if (first) p_res[b] = res;
 }
 
 // =============================================================================================
@@ -964,6 +1019,29 @@ int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void*
                            src, (const T*)x0, lambda, P.slot(0), P.slot(1), P.slot(2));
         HIP_TRY(hipGetLastError());
         return reduce3(lc.nblocks);
+    });
+}
+
+// |D x|_{2,1} and |q - proj(q + sigma_D D x)|^2 / sigma_D^2; reduce-only (include/pytv4d.h).  Always the one-site kernel, large planes
+// too: this runs once per convergence check, not once per iteration, so the plane-marching form would buy nothing worth a second kernel.
+int tv_cp_dual_residual(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, double sigma_D,
+                        double lambda, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (x == nullptr || q == nullptr || out == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
+    if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
+    if (!(sigma_D > 0.0) || !std::isfinite(sigma_D)) return fail(TV_E_ARG, "sigma_D must be a finite number > 0");
+    if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);                              // slot 0: |D x|_{2,1}, slot 1: the residual
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        hipLaunchKernelGGL((k_cp_res<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
+                           (const T*)q, (T)sigma_D, (T)(1.0 / lambda), 1.0 / (sigma_D * sigma_D), P.slot(0), P.slot(1));
+        HIP_TRY(hipGetLastError());
+        if (int rc = P.reduce(0, lc.nblocks, out, st)) return rc;
+        return P.reduce(1, lc.nblocks, out + 1, st);
     });
 }
 

@@ -233,6 +233,27 @@ template <int S, typename T, int V> struct NormEpi {
 };
 
 // Chambolle-Pock dual update, README.md:149-151 (with keepdims over the channel axis)
+// The arithmetic of one site: v = q + sigma D x per channel (q read at `base`), scale = 1 / max(1, |v|_2 / lambda) per column -- the new
+// q is v * scale; returns |D x|_2 summed over the columns.  ONE body for the update (CpDual) and for the reduce-only pass that measures
+// what the update would change (tv_cp_dual_residual, tv_kernels.hip: CpDualRes).
+template <int S, typename T, int V>
+__device__ __forceinline__ double cp_dual_site(const DG& g, const T* base, const Vec<T, V> (&o)[8], T sigma, T inv_lambda,
+                                               Vec<T, V> (&v)[8], Vec<T, V>& scale) {
+    Vec<T, V> vs = vsplat<T, V>(T(0));
+    for_each_channel<S>(g, [&](auto slot, int ch) {
+        constexpr int k = decltype(slot)::value;
+        v[k] = vload_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z) + sigma * o[k];
+        vs = vs + v[k] * v[k];
+    });
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        acc += (double)tsqrt(ds.v[i]);
+        scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * inv_lambda);
+    }
+    return acc;
+}
 template <int S, typename T, int V> struct CpDual {
     static constexpr bool REDUCES = true;
     T* q;
@@ -241,20 +262,8 @@ template <int S, typename T, int V> struct CpDual {
     __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
         T* base = q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
         Vec<T, V> v[8];
-        Vec<T, V> vs = vsplat<T, V>(T(0));
-        for_each_channel<S>(g, [&](auto slot, int ch) {
-            constexpr int k = decltype(slot)::value;
-            v[k] = vload_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z) + sigma * o[k];
-            vs = vs + v[k] * v[k];
-        });
-        const Vec<T, V> ds = sumsq_slots<T, V>(o);
         Vec<T, V> scale;
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            acc += (double)tsqrt(ds.v[i]);
-            scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * inv_lambda);
-        }
+        const double acc = cp_dual_site<S, T, V>(g, base, o, sigma, inv_lambda, v, scale);
         for_each_channel<S>(g, [&](auto slot, int ch) {
             constexpr int k = decltype(slot)::value;
             vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);

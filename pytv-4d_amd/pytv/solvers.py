@@ -24,7 +24,7 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "auto_pitch"]
+__all__ = ["ChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "auto_pitch", "operator_norm_sq"]
 
 
 def cp_step_size(nz_global, m, reg_z_over_reg, reg_time, time_weight_max=1.0):
@@ -44,6 +44,34 @@ def normal_spectral_bound(scheme, nz_global, m, reg_z_over_reg, reg_time, time_w
     t = m > 1 and reg_time > 0
     s = 2.0 + (reg_z_over_reg if z else 0.0) + (reg_time * time_weight_max if t else 0.0)
     return (1.0 if scheme == "central" else 4.0) * s
+
+
+def operator_norm_sq(A, AT, like, n_iter=20, seed=0, slab=None):
+    """Upper estimate of |A|^2 = lambda_max(A^T A) for a pair of callables on device tensors (``ChambollePockOperator``'s ``A`` / ``AT``):
+    ``n_iter`` steps of the power iteration v <- A^T A v / |A^T A v| from a seeded random image shaped like ``like``, the last |A^T A v|
+    (|v| = 1) times a safety factor of 1.05 -- the power iteration approaches lambda_max from below.  Returns a Python float.
+    ``n_iter`` calls of each operator, every scalar stays on the device: ONE host synchronisation per call, not one per iteration
+    (a sharded ``slab`` adds its all-reduce of one scalar per iteration; every rank gets the same number)."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("operator_norm_sq: n_iter must be >= 1")
+    gen = torch.Generator(device=like.device)
+    gen.manual_seed(int(seed) + (slab.rank if slab is not None else 0))
+    v = torch.randn(like.shape, dtype=like.dtype, device=like.device, generator=gen)
+
+    def norm(t):
+        s = torch.sum(torch.linalg.vector_norm(t, dtype=torch.float64) ** 2).reshape(1)
+        if slab is not None:
+            slab.allreduce_sum_(s)
+        return torch.sqrt(s)
+
+    v = v / norm(v).to(v.dtype)
+    lam = None
+    for _ in range(n_iter):
+        w = AT(A(v))
+        lam = norm(w)
+        v = w / torch.clamp_min(lam, torch.finfo(torch.float64).tiny).to(w.dtype)
+    return 1.05 * float(lam.item())
 
 
 def chebyshev_coefficients(lmax, n):
@@ -1029,13 +1057,22 @@ class ChambollePockOperator(_SlabProblem):
     shape, ``AT``: data -> image); they stay the user's code, the TV part runs in the HIP kernels.  ``A`` is applied ONCE by the
     constructor (the residual A x_init - b is carried from iteration to iteration); ``b`` must live on x_init's GPU.  ``tau`` must
     satisfy tau (sigma_A |A|^2 + sigma_D |D|^2) <= 1; the default assumes |A| <= 1.
+    ``norm_A``: |A| as a number, or ``"estimate"`` (``operator_norm_sq``: 20 power iterations on A^T A from a seeded random image, times
+    1.05); with ``tau=None`` the step is then tau = 1 / (sigma_A |A|^2 + sigma_D L), L = ``normal_spectral_bound`` >= |D|^2 -- the safe
+    choice for a projector whose norm is in the tens or hundreds, where the default step diverges.  ``norm_A=None`` (the default) leaves
+    tau exactly as it was; an explicit ``tau`` always wins.
+
+    How good is the iterate?  A duality gap is out of reach here (with a general A the dual objective needs (A^T A)^-1); ``residuals()``
+    gives the optimality (KKT) residual of the saddle problem the loop iterates on, ``run_until`` stops on it.
 
     With a ``slab`` (one process per GPU) ``x_init`` / ``b`` are this rank's z-slab of the image and its share of the data,
     ``A`` / ``AT`` act on the slab (operators that couple the slabs -- a cone-beam projector, say -- do their own
     communication inside the callables); the TV part trades the image / gradient halo planes like ``ChambollePock``."""
 
+    NORM_ITER = 20          # power iterations of norm_A="estimate"
+
     def __init__(self, A, AT, b, x_init, regularization, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0,
-                 mask_static=False, factor_reg_static=0, sigma_D=0.5, sigma_A=1.0, tau=None, slab=None, fused=None):
+                 mask_static=False, factor_reg_static=0, sigma_D=0.5, sigma_A=1.0, tau=None, slab=None, fused=None, norm_A=None):
         super().__init__(x_init, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab)
         if not isinstance(b, torch.Tensor) or not b.is_cuda or b.device != self.device:
             # b's raw pointer goes to HIP kernels (tv_cpop_residual, tv_cpop_p): a host tensor or one on another GPU would be a
@@ -1069,8 +1106,37 @@ class ChambollePockOperator(_SlabProblem):
         # for the dual update, once more for the loss of the new iterate -- the next iteration's first residual)
         self.r = torch.empty_like(self.b)
         self.n_A = self.n_AT = 0          # calls of the user's operators (tests assert one of each per iteration)
+        if isinstance(norm_A, str) and norm_A != "estimate":
+            raise ValueError("norm_A must be None, a number (|A|) or 'estimate'")
+        self.norm_A_sq = None
+        if norm_A is not None:
+            if isinstance(norm_A, str):
+                self.norm_A_sq = operator_norm_sq(self._count_A, self._count_AT, self.x, n_iter=self.NORM_ITER, slab=self.slab)
+            else:
+                self.norm_A_sq = float(norm_A) ** 2
+            if not (self.norm_A_sq >= 0.0) or self.norm_A_sq == float("inf"):
+                raise ValueError("norm_A must be a finite number >= 0 (estimate: A^T A v came out non-finite)")
+            if tau is None:
+                L = normal_spectral_bound(scheme, self.slab.nz_global, x_init.shape[1], reg_z_over_reg, reg_time, self.geo.time_weight_max)
+                self.tau = 1.0 / (self.sigma_A * self.norm_A_sq + self.sigma_D * L)
         self._fid0 = torch.zeros((), dtype=torch.float64, device=self.device)
         self._residual(self.x, self._fid0)
+        # calls the constructor made (the starting residual, the power iteration): n_A - n_A_setup == n_AT - n_AT_setup == iterations done
+        self.n_A_setup, self.n_AT_setup = self.n_A, self.n_AT
+        # optimality residual (``residuals``): the TV block of the starting triple is enqueued here, so that R_0 is that of the initial
+        # triple whenever ``run_until`` is called; read back (one synchronisation) only when somebody asks
+        self._steps = 0                   # step() calls: afterwards x_new holds the iterate the last step started from
+        self._res_scr = None              # data-space scratch of ``residuals``
+        self._res0 = self._residual_scalars(dual_zero=True)
+        self._R0 = None
+
+    def _count_A(self, v):
+        self.n_A += 1
+        return self._apply(self.A, v, self.b.shape, "A(x)")
+
+    def _count_AT(self, v):
+        self.n_AT += 1
+        return self._apply(self.AT, v, self.x.shape, "AT(p)")
 
     def _apply(self, op, v, shape, what):
         out = op(v)
@@ -1112,6 +1178,7 @@ class ChambollePockOperator(_SlabProblem):
                                              self.tau, 0, -1, _nv.ptr(self.ws), self.stream))
             self.x, self.x_new = self.x_new, self.x
             self._residual(self.x, out[1:2])
+            self._steps += 1
             return
         s.wait(h)
         _nv.check(self.lib.tv_cp_dual(g.ref, _nv.ptr(self.x), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
@@ -1124,6 +1191,7 @@ class ChambollePockOperator(_SlabProblem):
                                        _nv.ptr(atp), -self.tau, -self.tau, _nv.ptr(self.x_new), self.stream))
         self.x, self.x_new = self.x_new, self.x
         self._residual(self.x, out[1:2])
+        self._steps += 1
 
     def run(self, n_iter):
         hist = torch.zeros((n_iter, 2), dtype=torch.float64, device=self.device)
@@ -1132,6 +1200,108 @@ class ChambollePockOperator(_SlabProblem):
         self.slab.allreduce_sum_(hist)
         h = hist.cpu().numpy()
         return h[:, 1] + self.reg * h[:, 0]
+
+    # ---- optimality residual of the saddle problem (tv_cp_dual_residual) ---------------------------------------------------------------
+    _RES_DOC = """One ``step`` takes the triple (x, p, q) to
+            p+ = (p + sigma_A (A x - b)) / (1 + sigma_A),   q+ = proj_{|.|_2 <= reg}(q + sigma_D D x),   x+ = x - tau (A^T p+ + D^T q+)
+        and a triple is a saddle point of  min_x max_{p, |q| <= reg}  <A x - b, p> - 1/2 |p|^2 + <D x, q>  (whose x solves the problem) iff
+        A^T p + D^T q = 0, p = A x - b and q = proj(q + s D x) for one (equivalently every) s > 0.  The residual R = R_x + R_p + R_q:
+            R_x = |A^T p + D^T q|^2                              after a step: |x_before - x|^2 / tau^2 (one 2-word distance pass, no D^T)
+            R_p = |p - (A x - b)|^2                              two data-space vectors the solver carries
+            R_q = |q - proj(q + sigma_D D x)|^2 / sigma_D^2      the prox-gradient residual of the TV block: tv_cp_dual_residual, Nd + 1
+                                                                 words per voxel, what the next dual update would change, summed per site
+        R = 0 exactly at a saddle point, and nothing in it calls A or A^T.  fp32: R_x is a difference of iterates, resolved down to about
+        (eps_fp32 |x| / tau)^2 per voxel."""
+
+    def _residual_scalars(self, dual_zero=False):
+        """fp64 device words [|D x|_{2,1}, R_q, |x_before - x|^2 (or R_x itself before any step), R_p, 1/2 |A x - b|^2] of the current
+        triple on this rank; kernels and reductions are enqueued, nothing waits for them.  Touches the halo buffers (refilled by every
+        step before it reads them), the workspace and -- before the first step only -- x_new, never x, p, q or r.
+        dual_zero: the caller knows p = q = 0 (the constructor)."""
+        out = torch.zeros(5, dtype=torch.float64, device=self.device)
+        g, s, pl = self.geo, self.slab, self.plan
+        s.wait(pl.exchange_image(self.x, self.xh_prev, self.xh_next))
+        _nv.check(self.lib.tv_cp_dual_residual(g.ref, _nv.ptr(self.x), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q), self.sigma_D,
+                                               self.reg, out[0:2].data_ptr(), _nv.ptr(self.ws), self.stream))
+        if self._steps > 0:
+            # x_new holds the iterate the last step started from: the distance alone (out = NULL: nothing is stored)
+            _nv.check(self.lib.tv_axpby(g.ref, 1.0, _nv.ptr(self.x), 0.0, None, _nv.ptr(self.x_new), None, out[2:3].data_ptr(), _nv.ptr(self.ws),
+                                        self.stream))
+            p_zero = False
+        else:
+            # no previous x: p = q = 0 (what the constructor leaves) gives R_x = 0 without a call; a caller who has put a dual
+            # start into p / q pays one A^T and one D^T here (x_new is free before the first step)
+            p_zero = dual_zero or not bool(self.p.any())
+            if not (dual_zero or (p_zero and not bool(self.q.any()))):
+                atp = self._count_AT(self.p)
+                self.n_AT_setup += 1
+                s.wait(pl.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next)))
+                _nv.check(self.lib.tv_DT_axpy(g.ref, _nv.ptr(self.q), None, _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(atp), 1.0,
+                                              _nv.ptr(self.x_new), self.stream))
+                out[2] = torch.linalg.vector_norm(self.x_new, dtype=torch.float64) ** 2
+        if p_zero:
+            out[3] = torch.linalg.vector_norm(self.r, dtype=torch.float64) ** 2
+        else:
+            if self._res_scr is None:
+                self._res_scr = torch.empty_like(self.r)
+            torch.sub(self.p, self.r, out=self._res_scr)
+            out[3] = torch.linalg.vector_norm(self._res_scr, dtype=torch.float64) ** 2
+        out[4] = 0.5 * torch.linalg.vector_norm(self.r, dtype=torch.float64) ** 2
+        return out
+
+    def _residual_dict(self, out, stepped):
+        self.slab.allreduce_sum_(out)                    # the five scalars in one call
+        tv, rq, dx, rp, fid = (float(v) for v in out.cpu().tolist())
+        rx = dx / (self.tau * self.tau) if stepped else dx
+        return {"x": rx, "p": rp, "q": rq, "total": rx + rp + rq, "tv": tv, "fid": fid}
+
+    def residuals(self):
+        """{"x": R_x, "p": R_p, "q": R_q, "total": R, "tv": |D x|_{2,1}, "fid": 1/2 |A x - b|^2} of the current triple as Python floats,
+        between ``step`` / ``run`` calls.  Leaves x, p, q, r and the counters n_A / n_AT as they are (the one exception: asked before
+        the first step with a p or q the caller has made non-zero, R_x costs one A^T).  One host synchronisation.  Sharded: collective,
+        every rank calls it and gets the same numbers.
+        """
+        return self._residual_dict(self._residual_scalars(), self._steps > 0)
+    residuals.__doc__ += _RES_DOC
+
+    def initial_residual(self):
+        """R_0: ``residuals()["total"]`` of the triple the constructor left (enqueued there, read back on the first call)."""
+        if self._R0 is None:
+            self._R0 = self._residual_dict(self._res0, False)
+        return self._R0["total"]
+
+    def run_until(self, rel_res, max_iter, check_every=10):
+        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
+        first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the triple the constructor
+        left (x_init, p = q = 0); R_0 == 0 (a saddle point already) returns at once with ``converged=True``.
+        ``rel_res`` is RELATIVE TO THE STARTING POINT: the same number means a different accuracy from a different ``x_init`` -- a good
+        start has a small R_0 and is asked for more.  Compare ``residuals()["total"]`` itself across runs.
+        Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
+        ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one 2-word distance pass and three data-space reductions: no
+        call of A / A^T, and no host synchronisation between checks.  Both paths (``fused=True`` / ``False``).
+        """
+        import numpy as np
+        rel_res, max_iter, check_every = float(rel_res), int(max_iter), int(check_every)
+        if check_every < 1 or max_iter < 0:
+            raise ValueError("run_until: check_every must be >= 1 and the iteration limit >= 0")
+        r0 = self.initial_residual()
+        losses, done = [], 0
+        if r0 == 0.0:
+            res, converged = self.residuals(), True
+        else:
+            while True:
+                n = min(check_every, max_iter - done)
+                if n > 0:
+                    losses.append(np.asarray(self.run(n), dtype=np.float64))
+                    done += n
+                res = self.residuals()
+                converged = res["total"] <= rel_res * rel_res * r0
+                if converged or done >= max_iter:
+                    break
+        info = dict(iterations=done, converged=bool(converged), residuals=res, initial=r0,
+                    relative=float(np.sqrt(res["total"] / r0)) if r0 > 0.0 else 0.0)
+        return (np.concatenate(losses) if losses else np.zeros(0)), info
+    run_until.__doc__ += _RES_DOC
 
 
 # =================================================================================================

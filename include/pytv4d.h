@@ -182,6 +182,19 @@ int tv_cp_dual(const tv_geom* g, const void* x, const void* x_prev, const void* 
 int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x,
                  const void* x0, void* p, double tau, double sigma_A, double* fid, void* ws, void* stream);
 
+/* Primal step of the ACCELERATED Chambolle-Pock iteration (Chambolle & Pock 2011, Algorithm 2; the fidelity 1/2 |x - x0|^2 is 1-strongly
+ * convex, so its prox is closed-form and no fidelity dual p exists), with the extrapolation folded into the same pass:
+ *   x_new = (x - tau D^T q + tau x0) / (1 + tau);  x_bar = x_new + theta (x_new - x);  x = x_new;
+ *   *fid (device fp64) = 1/2 |x_new - x0|^2 of the local planes.  q_prev / q_next as y_prev / y_next in tv_DT.
+ * The dual step of the iteration is tv_cp_dual called on x_bar with that iteration's sigma; tau, sigma and theta of iteration k are host
+ * doubles (pytv.solvers.accel_schedule).  1 / (1 + tau) is formed once in double.  Every geometry tv_cp_primal takes (four schemes, fp32 /
+ * fp64, 16-byte lanes or scalar rows, pitched arrays -- pads stay zero --, mask_static / time_factor / time_weight_vol, z-slabs); fp32
+ * planes of >= 4 MiB take the plane-marching kernel: Nd + 4 words per voxel.
+ * x and x_bar must be different arrays, tau finite and > 0, theta finite and in [0, 1], else TV_E_ARG; a missing halo plane is TV_E_HALO;
+ * all checks precede any device access. */
+int tv_cp_primal_accel(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar,
+                       const void* x0, double tau, double theta, double* fid, void* ws, void* stream);
+
 /* Duality-gap certificate of the model every solver here minimises, P(x) = 1/2 |x - x0|^2 + lambda |D x|_{2,1}, for an iterate x and a dual
  * variable qs = qscale * q with |qs|_2 <= lambda per site (Chambolle-Pock: its q, qscale = 1; scaled-form ADMM: q = u, qscale = rho; both are
  * projections).  Over the local planes, with gd = D^T qs:

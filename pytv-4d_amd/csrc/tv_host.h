@@ -351,6 +351,9 @@ int DT_axpy(const tv_geom* g, const DG& d, const void* q, const void* qp, const 
             void* out, const void* base, double alpha, const void* base2 = nullptr, double beta = 0.0);
 int DT_cp_primal(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
                  float* x, const float* x0, float* p, float tau, float sigma_a, float inv_1p_sigma_a, double* partials);
+// accelerated primal step (tv_cp_primal_accel): x, x0 read once, x and x_bar written once -- Nd + 4 words per voxel
+int DT_cp_primal_accel(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
+                       float* x, float* x_bar, const float* x0, float tau, float inv_1p_tau, float theta, double* partials);
 // duality gap, reduce-only (tv_dual_gap): the D^T-side pass writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2, the D-side pass (same
 // grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to the first pass's sums
 int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,

@@ -8,7 +8,7 @@
 //                CpDual   -> q <- proj(q + sigma D x)            (tv_cp_dual)
 //                AdmmZU   -> z/u update of ADMM                  (tv_admm_zu)
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
-//                StoreDT / AxpyDT / CpPrimal epilogues           (tv_DT, tv_DT_axpy, tv_cp_primal)
+//                StoreDT / AxpyDT / CpPrimal / CpPrimalAccel epilogues   (tv_DT, tv_DT_axpy, tv_cp_primal, tv_cp_primal_accel)
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
 //   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
@@ -978,6 +978,38 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
         SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
         CpPrimal<T, V> epi{(T*)x, (const T*)x0, (T*)p, (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), P.slot(0)};
         hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimal<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
+        HIP_TRY(hipGetLastError());
+        return P.reduce(0, lc.nblocks, fid, st);
+    });
+}
+
+// Accelerated Chambolle-Pock primal step with the extrapolation folded in (include/pytv4d.h): tv_cp_primal's gather and launch rules with
+// the CpPrimalAccel epilogue.  Every argument check precedes the first device access.
+int tv_cp_primal_accel(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar, const void* x0,
+                       double tau, double theta, double* fid, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (q == nullptr || x == nullptr || x_bar == nullptr || x0 == nullptr || fid == nullptr || ws == nullptr)
+        return fail(TV_E_ARG, "NULL array");
+    if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
+    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
+    const double inv_1p_tau = 1.0 / (1.0 + tau);
+    if (march_ok(g, d, vec)) {
+        long long nb;
+        if (int rc = tvm::DT_cp_primal_accel(g, d, q, q_prev, q_next, st, &nb, (float*)x, (float*)x_bar, (const float*)x0, (float)tau,
+                                             (float)inv_1p_tau, (float)theta, P.slot(0))) return rc;
+        return P.reduce(0, nb, fid, st);
+    }
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
+        CpPrimalAccel<T, V> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)inv_1p_tau, (T)theta, P.slot(0)};
+        hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalAccel<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
         HIP_TRY(hipGetLastError());
         return P.reduce(0, lc.nblocks, fid, st);
     });

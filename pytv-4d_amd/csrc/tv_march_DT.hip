@@ -35,6 +35,10 @@ int DT_cp_primal(const tv_geom* g, const DG& d, const void* q, const void* qp, c
                  float* x, const float* x0, float* p, float tau, float sigma_a, float inv_1p_sigma_a, double* partials) {
     return launch_DT_march<CpPrimal, float>(g, d, q, qp, qn, st, nb, x, x0, p, tau, sigma_a, inv_1p_sigma_a, partials);
 }
+int DT_cp_primal_accel(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
+                       float* x, float* x_bar, const float* x0, float tau, float inv_1p_tau, float theta, double* partials) {
+    return launch_DT_march<CpPrimalAccel, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, inv_1p_tau, theta, partials);
+}
 int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
            const float* x, const float* x0, float qscale, double* partials) {
     return launch_DT_march<GapDT, float>(g, d, q, qp, qn, st, nb, x, x0, qscale, partials);

@@ -472,6 +472,33 @@ template <typename T, int V> struct CpPrimal {
     }
 };
 
+// Accelerated Chambolle-Pock primal step (Chambolle & Pock 2011, Algorithm 2, for the 1-strongly convex fidelity 1/2 |x - x0|^2):
+//   x_new = (x - tau D^T q + tau x0) / (1 + tau);  x_bar = x_new + theta (x_new - x);  x = x_new          (tv_cp_primal_accel)
+// inv_1p_tau = 1 / (1 + tau) is formed by the host in double.  x and x_bar are different arrays; pads stay zero (r, x, x0 are zero there).
+template <typename T, int V> struct CpPrimalAccel {
+    static constexpr bool REDUCES = true;
+    T* x;
+    T* x_bar;
+    const T* x0;
+    T tau, inv_1p_tau, theta;
+    double* partials;
+    __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
+        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        Vec<T, V> xn, xb;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            xn.v[i] = ((xv.v[i] - tau * r.v[i]) + tau * x0v.v[i]) * inv_1p_tau;
+            xb.v[i] = xn.v[i] + theta * (xn.v[i] - xv.v[i]);
+            const double e = (double)xn.v[i] - (double)x0v.v[i];
+            acc += 0.5 * e * e;
+        }
+        vstore_s<T, V>(x + off, xn);
+        vstore_s<T, V>(x_bar + off, xb);
+        return acc;
+    }
+};
+
 // =============================================================================================
 // duality gap of 1/2 |x - x0|^2 + lambda |D x|_{2,1} at (x, qs = qscale q), reduce-only (tv_dual_gap): with gd = D^T qs
 //   gap = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda |D x|_2 - <qs, D x> ]      both parts >= 0 site by site for |qs|_2 <= lambda

@@ -7,19 +7,23 @@ Its iteration (Chambolle 2004) differs from Chambolle-Pock 2011, so iterates dif
 """
 import torch
 
-from .solvers import ChambollePock
+from .solvers import AcceleratedChambollePock, ChambollePock
 from .tv_operators_GPU import _to_device
 
 __all__ = ["denoise_tv_chambolle"]
 
 
-def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None):
+def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
+                         accelerated=False):
     """Total-variation denoising of a 2-D (rows, cols) or 3-D (planes, rows, cols) image.
 
     weight : denoising weight (larger = smoother), as in scikit-image.
     eps    : stop when the relative change of the objective over ``check_every`` iterations drops below eps.
     rel_gap: None (the default) = the rule above; a number = stop when the duality gap certifies the answer instead,
              gap <= rel_gap * objective at a check (``ChambollePock.run_until``: 1/2 |u - u*|^2 <= gap); ``eps`` is then ignored.
+    accelerated: False (the default) = ``solvers.ChambollePock``; True = ``solvers.AcceleratedChambollePock`` (O(1/k^2): about a third of
+             the iterations to a given ``rel_gap`` for the one-sided schemes).  Its loss history is a progress indicator (the TV of the
+             extrapolated point), which is what the ``eps`` rule then watches; prefer ``rel_gap`` with it.
     Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point."""
     was_torch = isinstance(image, torch.Tensor)
     x, _ = _to_device(image)
@@ -29,7 +33,10 @@ def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, sch
         vol = x.reshape(x.shape[0], 1, x.shape[1], x.shape[2])
     else:
         raise ValueError("denoise_tv_chambolle: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
-    cp = ChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0)
+    if accelerated:
+        cp = AcceleratedChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0)
+    else:
+        cp = ChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0)
     prev, done = None, 0
     if rel_gap is not None:
         cp.run_until(rel_gap, max_num_iter, check_every)

@@ -270,6 +270,30 @@ int tv_cp_fixup(const tv_geom* g, const void* q, const void* q_prev, const void*
 int tv_cp_sweep(const tv_geom* g, const void* x_in, const void* x_prev, const void* x_next, const void* q_in, void* q_out, const void* x0,
                 void* p, void* x_out, double sigma_D, double lambda, double tau, double sigma_A, int32_t flags, int64_t chunk_begin,
                 int64_t chunk_count, double* tv, double* fid, void* ws, void* stream);
+/* One-sweep form of the ACCELERATED iteration (tv_cp_dual on x_bar + tv_cp_primal_accel; same geometries as tv_cp_fused:
+ * tv_cp_fused_supported), in the memory shape of tv_cp_sweep -- x_bar is the stencil input and is ping-ponged, the iterate x is the
+ * per-site array that is read and written in place, there is no fidelity dual p:
+ *   tv_cp_accel_sweep : q_out <- proj(q_in + sigma_D D xbar_in);  x_new = (x - tau D^T q_out + tau x0) / (1 + tau);
+ *                       xbar_out <- x_new + theta (x_new - x);  x <- x_new
+ *                       EXCEPT the adjoint terms tv_cp_fused leaves out;  *tv = |D xbar_in|_{2,1};  *fid = 1/2 |x_new - x0|^2 over the sites that
+ *                       are already complete; TV_CP_FID_OF_INPUT: *fid = 1/2 |x - x0|^2 of the x the call STARTED from, over all local sites;
+ *                       TV_CP_FID_BOTH: fid[0] that, fid[1] the flag-less partial (`fid` points to two doubles)
+ *   tv_cp_accel_fixup : adds the missing terms m to BOTH arrays (x_new and x_bar are affine in D^T q): x <- x - c m, xbar_out <- xbar_out - (1 + theta) c m
+ *                       with c = tau / (1 + tau), both coefficients formed in double; *fid = 1/2 |x - x0|^2 of the sites it visited, or 0 with
+ *                       x0 = NULL (a loop that takes the fidelity from the next sweep).  It takes q_out; q_prev / q_next as in tv_DT.
+ * q_in == q_out is the in-place update.  tau, theta (and sigma_D) are those of ONE iteration (pytv.solvers.accel_schedule); 1 / (1 + tau) is
+ * formed once in double.  2 Nd + 5 words per voxel where the kernel pair moves 3 Nd + 5.  Chunk / plane ranges, halos and flags as in
+ * tv_cp_sweep / tv_cp_fixup: q_out, x and xbar_out come out bit-identical however the chunks and planes are split over calls, and slabs
+ * cut at multiples of the unsharded tv_cp_zchunk() reproduce the unsharded x and xbar_out bit for bit (other cuts: to the rounding of the
+ * dtype; q_out always).  TV_E_ARG, each with its own message, before any device access: a NULL array (x0 may be NULL in the fix-up only),
+ * xbar_in == xbar_out, x aliasing xbar_in / xbar_out / x0, lambda not > 0, tau not finite or not > 0, theta not finite or outside [0, 1],
+ * unknown flags or TV_CP_FID_BOTH without TV_CP_FID_OF_INPUT, a geometry tv_cp_fused_supported refuses, arrays not 16-byte aligned.  A
+ * missing halo plane is TV_E_HALO. */
+int tv_cp_accel_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
+                      const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double tau, double theta, int32_t flags,
+                      int64_t chunk_begin, int64_t chunk_count, double* tv, double* fid, void* ws, void* stream);
+int tv_cp_accel_fixup(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* xbar_out, const void* x0,
+                      double tau, double theta, int64_t z_begin, int64_t z_count, double* fid, void* ws, void* stream);
 
 /* ---- fused ADMM updates (not in the reference; README.md:26,135 mention only) --------------- */
 /* v = D x + u; z = v * max(0, 1 - thresh/|v|_2); u = v - z; *tv (device fp64) = |D x|_{2,1}. */

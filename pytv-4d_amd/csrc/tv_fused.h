@@ -295,6 +295,24 @@ template <typename T, int V> __device__ __forceinline__ Vec<T, V> cp_shfl_down(c
     return r;
 }
 
+// |D x|_2^2 per column for the TV partial of the sweep, with the order of its roundings PINNED: o_0^2 rounded, then one fused multiply-add
+// per further slot.  Written as `s + o * o` (sumsq_slots) the first two terms are fadd(fmul, fmul), which the compiler may contract either
+// way round, and two instantiations of this kernel did: *tv of the ALG_CPACC sweep differed from the ALG_CP one's in the 11th digit on
+// the same input (hybrid, 2 frames, fp32).  NS: slots the scheme uses (the others are exactly zero); an inactive axis adds fma(0, 0, s) = s.
+__device__ __forceinline__ float tfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double tfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template <int NS, typename T, int V> __device__ __forceinline__ Vec<T, V> sumsq_slots_pinned(const Vec<T, V> (&o)[8]) {
+    Vec<T, V> s;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        T a = o[0].v[i] * o[0].v[i];
+#pragma unroll
+        for (int k = 1; k < NS; ++k) a = tfma(o[k].v[i], o[k].v[i], a);
+        s.v[i] = a;
+    }
+    return s;
+}
+
 template <typename T> struct FusedArgsT {
     const T* x_in;
     const T* xp;          // plane z0-1 of x_in (or nullptr)
@@ -303,11 +321,12 @@ template <typename T> struct FusedArgsT {
     const T* x0;
     T* p;
     T* x_out;
-    T sigma, inv_lambda, tau, sigma_a, inv_1p_sigma_a;
+    T sigma, inv_lambda, tau, sigma_a, inv_1p_sigma_a;      // ALG_CPACC: sigma_a holds theta, inv_1p_sigma_a holds 1 / (1 + tau)
     double* part_tv;
     double* part_fid;
     int full_store;       // ALG_ADMM: bit 0 = every sample of t' is stored (z stays recoverable; else only what the fix-up reads), bit 1 = the second partial is |x - x0|^2
                           // ALG_CP: bit 1 = the second partial is 1/2 |x_in - x0|^2 over all sites (TV_CP_FID_OF_INPUT)
+                          // ALG_CPACC: the same bits, with the iterate x (the array `p`) in the place of x_in
     const T* q_in;        // where the dual variable is READ (round 4: q ping-pong, tv_cp_sweep; == q: in place, as before).  Reading one
                           // array and writing another is ~9 % faster than the in-place read-modify-write for this kernel's memory shape
                           // (tools/archive/bwtest4 variant 4: 5.98 against 5.50 TB/s) -- the price is a second q array
@@ -328,7 +347,13 @@ using FusedArgs = FusedArgsT<float>;
 //   ALG_CPOP (round 3): Chambolle-Pock with a user-supplied data-fidelity operator A (README.md:2,148; solvers.ChambollePockOperator):
 //            the dual update of ALG_CP and x_out <- x - tau A^T p - tau D^T q' one plane behind; `p` is the image A^T p (read only),
 //            x0 is not touched, the second partial is unused.  Its fix-up is the ALG_ADMM one with the coefficient tau.
-constexpr int ALG_CP = 0, ALG_ADMM = 1, ALG_CPOP = 2;
+//   ALG_CPACC: the accelerated iteration (Chambolle & Pock 2011, Algorithm 2) in the memory shape of ALG_CP.  The
+//            stencil input x_in is the extrapolated point x_bar, the per-site read-and-write array `p` is the iterate x, x_out receives
+//            the next x_bar:  q <- proj(q + sigma D x_bar);  x_new = (x - tau D^T q' + tau x0) / (1 + tau)  (the arithmetic of CpPrimalAccel,
+//            tv_stencil.h);  x_bar_out = x_new + theta (x_new - x);  x <- x_new in place.  theta travels in sigma_a, 1 / (1 + tau) in
+//            inv_1p_sigma_a.  Partials as ALG_CP with x in the role of the iterate.  x_new and x_bar are both affine in D^T q', so the
+//            fix-up adds the missing terms to BOTH arrays (FixupArgsT::x_out2 / tau2).
+constexpr int ALG_CP = 0, ALG_ADMM = 1, ALG_CPOP = 2, ALG_CPACC = 3;
 
 // XW: the CP_NW waves of a block exchange their tile-edge column terms through LDS (one barrier per plane)
 // TWIN: time windows for volumes with more than CP_TWN frames -- grid z = window, the block works on the frames
@@ -436,12 +461,16 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
     // finalise plane zf (its x values are in `xv`), adjoint accumulator `racc` (un-scaled)
     // PFX (round 5): the operands of the lagged primal update (x0, p of plane z - 1) are requested at the TOP of the frame that finalises them,
     // through frame descriptors (no branch), instead of inside finalize() behind everything else: one exposed memory round trip per frame
-    // less.  pre0 / pre1: those operands when `pre` is set (x0 and p; ADMM: x0; CPOP: A^T p).  Measured with the product library and a
+    // less.  pre0 / pre1: those operands when `pre` is set (x0 and p; ADMM: x0; CPOP: A^T p; CPACC: x0 and x).  Measured with the product library and a
     // -DTV_FUSED_PFX=1 variant interleaved on one box, 24 constructions of the north-star problem each (profiles/r5i_pfx_ab.txt): hybrid
     // sweep 32.8 -> 31.8 ms on average, best allocation 31.0 -> 30.7; ADMM hybrid 14.11 -> 14.01 ms, upwind 10.66 -> 10.48.  Not for central
     // (its M = 8 instantiations spill 36 - 100 B with it) nor the hybrid single-window instantiations for 6 - 8 frames (12 - 88 B).
+    // ALG_CPACC: not for the downwind single-window instantiation of 8 frames either (36 B with it, where its ALG_CP sibling has none:
+    // profiles/cp_accel_sweep_regs.txt).  (The spill figures above are those of the rounds that measured them; the table in that file
+    // is the kernel as it is now, sumsq_slots_pinned included.)
     constexpr bool PFX = (TV_FUSED_PFX != 0) && XW && sizeof(T) == 4 &&
-                         (S == UPWIND || S == DOWNWIND || (S == HYBRID && (TWIN || M <= 5)));
+                         (S == UPWIND || S == DOWNWIND || (S == HYBRID && (TWIN || M <= 5))) &&
+                         !(ALG == ALG_CPACC && S == DOWNWIND && !TWIN && M == 8);
     auto finalize = [&](int zf, int t, const VT& xv, VT racc, bool pre = false, const VT& pre0 = VT{}, const VT& pre1 = VT{}) {
         if (!c.ok || t0 + t >= Mg) return;
         const int eb = (zf - c.zs) & 1;
@@ -479,12 +508,22 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
         const VT x0v = (PFX && pre) ? pre0 : ldu_s_t<T, V>(a.x0 + foff, voff), pv = (PFX && pre) ? pre1 : ldu_s_t<T, V>(a.p + foff, voff);
         VT pn, xo;
         double e2 = 0.0;
+        if constexpr (ALG == ALG_CPACC) {     // pv is the iterate x, xv (x_bar) is not used: pn = x_new (in place), xo = the next x_bar
 #pragma unroll
-        for (int i = 0; i < V; ++i) {
-            pn.v[i] = (pv.v[i] + a.sigma_a * (xv.v[i] - x0v.v[i])) * a.inv_1p_sigma_a;
-            xo.v[i] = (xv.v[i] - a.tau * pn.v[i]) - a.tau * (s * racc.v[i]);
-            const double e = (double)xo.v[i] - (double)x0v.v[i];
-            e2 += 0.5 * e * e;
+            for (int i = 0; i < V; ++i) {
+                pn.v[i] = ((pv.v[i] - a.tau * (s * racc.v[i])) + a.tau * x0v.v[i]) * a.inv_1p_sigma_a;
+                xo.v[i] = pn.v[i] + a.sigma_a * (pn.v[i] - pv.v[i]);
+                const double e = (double)pn.v[i] - (double)x0v.v[i];
+                e2 += 0.5 * e * e;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                pn.v[i] = (pv.v[i] + a.sigma_a * (xv.v[i] - x0v.v[i])) * a.inv_1p_sigma_a;
+                xo.v[i] = (xv.v[i] - a.tau * pn.v[i]) - a.tau * (s * racc.v[i]);
+                const double e = (double)xo.v[i] - (double)x0v.v[i];
+                e2 += 0.5 * e * e;
+            }
         }
         stu_s_t<T, V>(a.p + foff, voff, pn);
         stu_s_t<T, V>(a.x_out + foff, voff, xo);
@@ -500,10 +539,11 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
             // in registers, so the fix-up no longer has to read x0 for the sites it completes -- the solver takes 1/2 |x_k - x0|^2
             // from sweep k (README.md:157 pairs it with the TV of x_{k-1}, which sweep k - 1 delivered).  TV_CP_FID_BOTH (round 5): the
             // fidelity of the OUTPUT over the complete sites goes to the second accumulator as well (the fix-up, called with x0, adds the rest)
+            const VT& xin = (ALG == ALG_CPACC) ? pv : xv;      // the iterate this sweep started from
             double f2 = 0.0;
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                const double e = (double)xv.v[i] - (double)x0v.v[i];
+                const double e = (double)xin.v[i] - (double)x0v.v[i];
                 f2 += 0.5 * e * e;
             }
             add1 = f2;
@@ -568,7 +608,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
                 constexpr int NTX = TV_FUSED_NT ? BUF_NT : 0;
                 if constexpr (ALG == ALG_CPOP) fx0 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.p + fo, z > c.zs, fb), bo);
                 else fx0 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.x0 + fo, z > c.zs, fb), bo);
-                if constexpr (ALG == ALG_CP) fx1 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.p + fo, z > c.zs, fb), bo);
+                if constexpr (ALG == ALG_CP || ALG == ALG_CPACC) fx1 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.p + fo, z > c.zs, fb), bo);
             }
             VT qcur[PFQ ? 4 : 1];
             if (PFQ) {
@@ -659,7 +699,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
                     v[k] = (ALG == ALG_ADMM) ? o[k] + qv : qv + a.sigma * o[k];
                     vs = vs + v[k] * v[k];
                 });
-                const VT ds = sumsq_slots<T, V>(o);
+                const VT ds = sumsq_slots_pinned<(S == HYBRID) ? 8 : 4, T, V>(o);
                 VT scale;
                 if constexpr (ALG == ALG_ADMM) {
                     // group soft threshold, the arithmetic of AdmmZU (tv_stencil.h): z = v scale, u = v - z, t = z - u
@@ -792,7 +832,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
     if (threadIdx.x == 0 && threadIdx.y == 0) a.part_tv[linear_block_id()] = acc_tv;
     acc_fid = block_sum(acc_fid, sm);
     if (threadIdx.x == 0 && threadIdx.y == 0) a.part_fid[linear_block_id()] = acc_fid;
-    if constexpr (ALG == ALG_CP) {
+    if constexpr (ALG == ALG_CP || ALG == ALG_CPACC) {
         if (a.full_store & 4) {               // uniform
             acc_fid2 = block_sum(acc_fid2, sm);
             if (threadIdx.x == 0 && threadIdx.y == 0) a.part_fid2[linear_block_id()] = acc_fid2;
@@ -813,6 +853,8 @@ template <typename T> struct FixupArgsT {
     const T* x0;
     T tau;
     int chunk0;           // class 1: first chunk whose edge planes are visited
+    T* x_out2 = nullptr;  // ALG_CPACC: the second array the missing terms are added to (x_bar), with its own coefficient
+    T tau2 = T(0);
 };
 using FixupArgs = FixupArgsT<float>;
 
@@ -835,6 +877,8 @@ template <typename T, int V> __device__ __forceinline__ void FXST(T* p, const Ve
 #endif
 }
 // ALG_ADMM: `q` is the array of t', `x_out` the residual r, tau = -rho (r += rho s m), the returned partial is r^2 (no x0)
+// ALG_CPACC: m is gathered once and subtracted twice -- x_out (the iterate x) -= tau (s m), x_out2 (x_bar) -= tau2 (s m), with
+// tau = tau_k / (1 + tau_k) and tau2 = (1 + theta_k) tau (formed by the host in double); the returned partial is 1/2 |x - x0|^2
 template <int S, bool XW, typename T = float, int ALG = ALG_CP>
 __device__ __forceinline__ double fixup_site(const DG& g, const WT<T>& w, const FixupArgsT<T>& a, int zchunk, int zl, int t, int y,
                                              int col0) {
@@ -880,17 +924,24 @@ __device__ __forceinline__ double fixup_site(const DG& g, const WT<T>& w, const 
     const T s = (S == HYBRID) ? Consts<T>::inv_sqrt2() : (CEN ? T(0.5) : T(1));
     const long long off = (long long)zl * g.s_z + inpl;
     const VT xv = FXLD<T, V>(a.x_out + off);
-    VT x0v = zero;
-    if constexpr (ALG == ALG_CP) { if (a.x0 != nullptr) x0v = FXLD<T, V>(a.x0 + off); }      // x0 NULL: the caller takes the fidelity elsewhere
+    VT x0v = zero, bv = zero;
+    if constexpr (ALG == ALG_CPACC) bv = FXLD<T, V>(a.x_out2 + off);
+    if constexpr (ALG == ALG_CP || ALG == ALG_CPACC) { if (a.x0 != nullptr) x0v = FXLD<T, V>(a.x0 + off); }      // x0 NULL: the caller takes the fidelity elsewhere
     VT xo;
     double acc = 0.0;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         xo.v[i] = xv.v[i] - a.tau * (s * m.v[i]);
         const double e = (double)xo.v[i] - (double)x0v.v[i];
-        acc += (ALG == ALG_CP ? 0.5 : 1.0) * e * e;
+        acc += (ALG == ALG_ADMM ? 1.0 : 0.5) * e * e;
     }
     FXST<T, V>(a.x_out + off, xo);
+    if constexpr (ALG == ALG_CPACC) {
+        VT bo;
+#pragma unroll
+        for (int i = 0; i < V; ++i) bo.v[i] = bv.v[i] - a.tau2 * (s * m.v[i]);
+        FXST<T, V>(a.x_out2 + off, bo);
+    }
     return acc;
 }
 

@@ -241,6 +241,56 @@ int tv_cp_fixup(const tv_geom* g, const void* q, const void* q_prev, const void*
                              });
 }
 
+// One-sweep ACCELERATED Chambolle-Pock (tv_fused.h, ALG_CPACC; include/pytv4d.h): the dual update of tv_cp_sweep on the extrapolated point and the
+// closed-form primal step with its extrapolation one plane behind.  Every argument check precedes the first device access.
+static int cp_accel_steps_ok(double tau, double theta) {
+    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    return 0;
+}
+
+int tv_cp_accel_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
+                      const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double tau, double theta, int32_t flags,
+                      int64_t chunk_begin, int64_t chunk_count, double* tvout, double* fid, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (!xbar_in || !q_in || !q_out || !x0 || !x || !xbar_out || !tvout || !fid || !ws) return fail(TV_E_ARG, "NULL array");
+    if (xbar_in == xbar_out) return fail(TV_E_ARG, "xbar_in and xbar_out must be different buffers (ping-pong)");
+    if (x == xbar_in || x == xbar_out || x == x0) return fail(TV_E_ARG, "x must not alias xbar_in, xbar_out or x0");
+    if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
+    if (int rc = cp_accel_steps_ok(tau, theta)) return rc;
+    if (flags & ~(TV_CP_FID_OF_INPUT | TV_CP_FID_BOTH)) return fail(TV_E_ARG, "tv_cp_accel_sweep: unknown flag");
+    if ((flags & TV_CP_FID_BOTH) && !(flags & TV_CP_FID_OF_INPUT)) return fail(TV_E_ARG, "tv_cp_accel_sweep: TV_CP_FID_BOTH extends TV_CP_FID_OF_INPUT");
+    if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
+    if (!aligned16({xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
+    const double inv_1p_tau = 1.0 / (1.0 + tau);
+    auto args = [&]<typename T>(const Partials& P) {          // theta and 1 / (1 + tau) in the fields of sigma_A; slot 2: TV_CP_FID_BOTH only
+        return FusedArgsT<T>{(const T*)xbar_in, (const T*)xbar_prev, (const T*)xbar_next, (T*)q_out, (const T*)x0, (T*)x,
+                             (T*)xbar_out, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)theta, (T)inv_1p_tau, P.slot(0), P.slot(1),
+                             ((flags & TV_CP_FID_OF_INPUT) ? 2 : 0) | ((flags & TV_CP_FID_BOTH) ? 4 : 0), (const T*)q_in, P.slot(2)};
+    };
+    return run_sweep<ALG_CPACC>(g, d, xbar_in, xbar_prev, xbar_next, chunk_begin, chunk_count, ws, (hipStream_t)stream, tvout, fid,
+                                (flags & TV_CP_FID_BOTH) ? 2 : 1, args);
+}
+
+// its fix-up: the missing adjoint terms m go to both arrays, x -= c (s m) and x_bar -= (1 + theta) c (s m) with c = tau / (1 + tau)
+int tv_cp_accel_fixup(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* xbar_out, const void* x0,
+                      double tau, double theta, int64_t z_begin, int64_t z_count, double* fid, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (!q || !x || !xbar_out || !fid || !ws) return fail(TV_E_ARG, "NULL array");      // x0 may be NULL: no fidelity (*fid = 0)
+    if (x == xbar_out || x == x0) return fail(TV_E_ARG, "x must not alias xbar_out or x0");
+    if (int rc = cp_accel_steps_ok(tau, theta)) return rc;
+    if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
+    if (!aligned16({q, q_prev, q_next, x, xbar_out, x0})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
+    const double c = tau / (1.0 + tau), cb = (1.0 + theta) * c;
+    return run_fixup<ALG_CPACC>(g, d, q, q_prev, q_next, z_begin, z_count, Partials(ws, d), (hipStream_t)stream, fid, x0 != nullptr,
+                                [&]<typename T>(const FixPlan& fp) {
+                                    return FixupArgsT<T>{(const T*)q, (const T*)q_prev, (const T*)q_next, (T*)x, (const T*)x0, (T)c, fp.chunk_lo,
+                                                         (T*)xbar_out, (T)cb};
+                                });
+}
+
 // One-sweep ADMM (tv_fused.h, ALG_ADMM): the z / u update of the outer iteration that ends and the residual of the x-solve that
 // starts, from ONE pass over u (build-defined, the reference ships no ADMM; README.md:26,135).
 int tv_admm_fused(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* u, void* t, const void* x0, void* r,

@@ -1,5 +1,6 @@
 // tv_fused_launch.h -- launch templates of the one-sweep kernels (tv_fused.h).  One (dtype, ALG) pair per translation unit
-// (tv_fused.hip: float CP, tv_fused_f64.hip: double CP, tv_fused_admm.hip / tv_fused_admm_f64.hip: ADMM) so that the four
+// (tv_fused.hip: float CP, tv_fused_f64.hip: double CP, tv_fused_admm.hip / tv_fused_admm_f64.hip: ADMM, tv_fused_cpop*.hip: the
+// operator sweep, tv_fused_cpacc*.hip: the accelerated iteration) so that the
 // sets of instantiations compile next to each other; the extern "C" entry points and the launch geometry live in tv_fused.hip.
 #pragma once
 #include "tv_host.h"
@@ -21,7 +22,7 @@ inline constexpr const char* kNoFusedSM = "unsupported (scheme, M) for the one-s
 template <typename T, int ALG>
 static int fused_sweep_launch(const tv_geom* g, const DG& d, const LC& lc, hipStream_t st, const FusedArgsT<T>& a, int zc, int chunk0, bool xw,
                               bool force_win) {
-    if (ALG != ALG_CP && !xw) return fail(TV_E_ARG, "the ADMM / operator sweeps are built with TV_FUSED_XW=1 only");
+    if (ALG != ALG_CP && !xw) return fail(TV_E_ARG, "the ADMM / operator / accelerated sweeps are built with TV_FUSED_XW=1 only");
     return dispatch_scheme_m(WindowedMs{}, g->scheme, (d.m > CP_TWN || force_win) ? 0 : d.m, kNoFusedSM, [&]<int S, int M>() -> int {
         if constexpr (M == 0) {          // M > 8: windows of 8 frames
             if (xw) hipLaunchKernelGGL((k_cp_fused<S, CP_TWN, true, true, T, ALG>), lc.grid, lc.block, 0, st, d, make_w<T>(g), a, zc, chunk0);
@@ -37,7 +38,7 @@ static int fused_sweep_launch(const tv_geom* g, const DG& d, const LC& lc, hipSt
 
 template <typename T, int ALG>
 static int fused_fixup_launch(const tv_geom* g, const DG& d, hipStream_t st, const FixupArgsT<T>& a, const FixPlan& p, double* w0) {
-    if (ALG != ALG_CP && !p.xw) return fail(TV_E_ARG, "the ADMM / operator sweeps are built with TV_FUSED_XW=1 only");
+    if (ALG != ALG_CP && !p.xw) return fail(TV_E_ARG, "the ADMM / operator / accelerated sweeps are built with TV_FUSED_XW=1 only");
     const dim3 blk(64, 4, 1);
     return dispatch_scheme(g->scheme, [&]<int S>() -> int {
         auto launch = [&]<bool XW>() -> int {

@@ -9,6 +9,7 @@ fused HIP kernels (include/pytv4d.h):
                         or the pair tv_cp_dual (D + sigma-step + projection, TV partial) (1+2Nd)
                         + tv_cp_primal (fidelity dual + D^T + primal step, loss partial)  (Nd+5)
     AcceleratedChambollePock  tv_cp_dual on the extrapolated point + tv_cp_primal_accel (D^T, closed-form fidelity prox, extrapolation)  (Nd+4)
+                        or tv_cp_accel_sweep + tv_cp_accel_fixup (one sweep, 5+2Nd words/voxel + fix-up)
                         with the step schedule of Chambolle & Pock 2011, Algorithm 2: O(1/k^2) instead of O(1/k)
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
     ADMM                tv_admm_tu / tv_admm_zu, tv_DT_axpy, tv_normal_op2 (I + rho D^T D from x alone, two dot products) +
@@ -1082,18 +1083,26 @@ class AcceleratedChambollePock(_SlabProblem):
         x_new <- (x - tau_k D^T q + tau_k x0) / (1 + tau_k)
         x_bar <- x_new + theta_k (x_new - x);  x <- x_new                           tv_cp_primal_accel, one pass (Nd + 4)
 
-    The scalars of iteration k are host doubles passed to the two launches: no device-resident table, no hipGraph capture, no persistent
-    small-volume form and no one-sweep form -- two launches (plus their reductions) per iteration on every volume.  What that costs:
-    3 Nd + 5 words per voxel against 2 Nd + 5 of ``ChambollePock``'s one-sweep kernel at large volumes, and a launch per kernel against
-    the persistent loop of ``ChambollePock`` at the reference's small shapes: the gain is iterations saved, not
-    time per iteration.
+    That kernel pair moves 3 Nd + 5 words per voxel.  The ONE-SWEEP path (``set_fused``, ``fused``) runs the same iteration as
+    tv_cp_accel_sweep + tv_cp_accel_fixup -- ``ChambollePock``'s one-sweep kernel with another epilogue: x_bar is the stencil input and is
+    ping-ponged with a second buffer, x is updated in place, q is read and written once: 2 Nd + 5 words.  The state (x, x_bar, q) is the same
+    on both paths, so ``set_fused`` may be called between iterations at any time.  DEFAULT: ``ChambollePock``'s rule -- the sweep where
+    tv_cp_fused_supported accepts the geometry, the volume is not sharded and holds at least 1024 * TV_FUSED_MIN_KVOXELS (16 Mi) voxels, the
+    pair otherwise.  Measured on 64x8x1024x1024 fp32 (profiles/cp_accel_sweep_bench.txt): the sweep path takes 0.65 -
+    0.81 of the pair's time per iteration in all four schemes and 1.00 - 1.05 of ``ChambollePock``'s one-sweep iteration.
+
+    The scalars of iteration k are host doubles passed to the launches.  Not built: hipGraph capture, a device-resident step table, the
+    placement tuner / arena of ``ChambollePock``, a persistent small-volume form, and the sweep / exchange / fix-up schedule of a sharded slab
+    (slabs run the kernel pair) -- at the reference's small shapes the solver pays a launch per kernel against the persistent loop of
+    ``ChambollePock``.
 
     gamma = 0 gives theta = 1 and constant steps (Algorithm 1 with extrapolation).  The step schedule continues across ``run`` /
     ``run_steps`` / ``step`` calls (``self.it`` counts the iterations done); ``reset()`` starts it again.
     Sharded (``slab``): the boundary plane(s) of x_bar travel before the dual kernel and those of q before the primal kernel, both waits
     exposed (no interior / edge overlap).
 
-    Per-step scalars: the slots of ``ChambollePock`` -- TV in slot 0, fidelity in slot ``F``."""
+    Per-step scalars: the slots of ``ChambollePock`` -- TV in slot 0, fidelity in slot ``F`` (one-sweep path: the sweep's part in slot ``F``,
+    the fix-up's in ``F + 1``; they are summed when the loss is asked for)."""
 
     SLOTS = ChambollePock.SLOTS
     F = ChambollePock.F
@@ -1138,6 +1147,29 @@ class AcceleratedChambollePock(_SlabProblem):
         self.it = 0
         self._scratch = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
         self._sched = None
+        self.x_bar_alt = None            # ping-pong partner of x_bar on the one-sweep path, allocated on first use
+        self.set_fused(None)
+
+    @property
+    def fused(self):
+        """True: iterations run as tv_cp_accel_sweep + tv_cp_accel_fixup; False: as tv_cp_dual + tv_cp_primal_accel (``set_fused``)"""
+        return self._fused
+
+    def set_fused(self, fused):
+        """Choose the path of the iterations that follow.  True = the one-sweep kernel (ValueError where tv_cp_fused_supported refuses the
+        geometry, and on a sharded slab: the sweep / exchange / fix-up schedule of slabs is not built for this solver), False = the kernel
+        pair, None = the construction default (class docstring).  The state is untouched; ``reset()`` keeps the choice."""
+        supported = bool(self.lib.tv_cp_fused_supported(self.geo.ref))
+        if fused is None:
+            # ``ChambollePock``'s rule: supported, unsharded, enough voxels to fill the GPU with the sweep's blocks (TV_FUSED_MIN_KVOXELS)
+            fused = supported and not self.slab.sharded and self.x0.numel() >= 1024 * _nv.get_option("TV_FUSED_MIN_KVOXELS", 16384)
+        elif fused:
+            if not supported:
+                raise ValueError("the one-sweep kernel does not support this geometry (tv_cp_fused_supported: whole 16-byte lanes or pitched "
+                                 "rows, Nx >= 64, frames below 2^31 bytes)")
+            if self.slab.sharded:
+                raise ValueError("set_fused(True): the one-sweep path of AcceleratedChambollePock takes unsharded volumes only")
+        self._fused = bool(fused)
 
     def _steps(self, k):
         """(tau_k, sigma_k, theta_k) as Python floats, from a cached ``accel_schedule`` that grows by doubling"""
@@ -1148,7 +1180,7 @@ class AcceleratedChambollePock(_SlabProblem):
         return float(tau[k]), float(sigma[k]), float(theta[k])
 
     def reset(self):
-        """Back to the state of a fresh solver: x = x_bar = x0, q = 0, and the step schedule at iteration 0."""
+        """Back to the state of a fresh solver: x = x_bar = x0, q = 0, and the step schedule at iteration 0.  The path (``fused``) stays."""
         self.x.copy_(self.x0)
         self.x_bar.copy_(self.x0)
         self.q.zero_()
@@ -1160,6 +1192,19 @@ class AcceleratedChambollePock(_SlabProblem):
         out = self._scratch if out is None else out
         tau, sigma, theta = self._steps(self.it)
         s, pl, F = self.slab, self.plan, self.F
+        if self._fused:
+            # one sweep over all chunks (x_bar -> x_bar_alt, x and q in place), one fix-up over all planes; both return a part of the fidelity
+            if self.x_bar_alt is None:
+                self.x_bar_alt = self.new_image()
+            g, ws, st = self.geo.ref, _nv.ptr(self.ws), self.stream
+            _nv.check(self.lib.tv_cp_accel_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
+                                                 _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), sigma, self.reg, tau, theta, 0, 0, -1,
+                                                 out[0:1].data_ptr(), out[F:F + 1].data_ptr(), ws, st))
+            _nv.check(self.lib.tv_cp_accel_fixup(g, _nv.ptr(self.q), None, None, _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), _nv.ptr(self.x0),
+                                                 tau, theta, 0, -1, out[F + 1:F + 2].data_ptr(), ws, st))
+            self.x_bar, self.x_bar_alt = self.x_bar_alt, self.x_bar
+            self.it += 1
+            return
         s.wait(pl.exchange_image(self.x_bar, self.xh_prev, self.xh_next))
         _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
                                       sigma, self.reg, out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))

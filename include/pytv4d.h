@@ -379,6 +379,8 @@ int tv_axpby(const tv_geom* g, double a, const void* x, double b, const void* y,
  *     sc[2] = gamma of the previous step,  sc[3] = alpha of the previous step; sc[3] == 0 marks the FIRST step of a solve
  *   beta = first ? 0 : gamma / gamma_old;   alpha = gamma / (first ? delta : delta - beta gamma / alpha_old)
  *   d = r + beta d;  s = w + beta s (= A d);  x += alpha d;  r -= alpha s;   then sc[2] = gamma, sc[3] = alpha
+ * Breakdown: gamma_old <= 0 gives beta = 0, and a denominator <= 0 gives alpha = 0 -- d and s still advance, x and r are left as they
+ * are, and sc[3] is stored as 1e-300 instead of 0, so that the next step of the solve is not taken for a first step.
  * x0 != NULL: *fid = 1/2 |x_new - x0|^2 (the ADMM loss after the last step, for one extra read). */
 int tv_cg_update(const tv_geom* g, void* x, void* r, void* d, void* s, const void* w, double* sc, const void* x0, double* fid,
                  void* ws, void* stream);
@@ -388,7 +390,9 @@ int tv_admm_tu(const tv_geom* g, const void* x, const void* x_prev, const void* 
                double thresh, double* tv, void* ws, void* stream);
 /* Conjugate-gradient vector updates with device-resident scalars (no host round trip):
  *   tv_cg_step1: alpha = rs/dAd;  x += alpha d;  r -= alpha Ad;  *rs_new = <r, r>
- *   tv_cg_step2: beta = rs_new/rs; d = r + beta d                                            */
+ *   tv_cg_step2: beta = rs_new/rs; d = r + beta d
+ * Breakdown: tv_cg_step1 with dAd <= 0 takes alpha = 0 -- x and r are left as they are and *rs_new = <r, r> of the unchanged r.
+ * tv_cg_step2 with rs <= 0 takes beta = 0 -- d becomes r, a restart from the steepest-descent direction. */
 int tv_cg_step1(const tv_geom* g, void* x, void* r, const void* d, const void* Ad, const double* rs,
                 const double* dAd, double* rs_new, void* ws, void* stream);
 int tv_cg_step2(const tv_geom* g, void* d, const void* r, const double* rs_new, const double* rs, void* stream);

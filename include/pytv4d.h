@@ -195,6 +195,32 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
 int tv_cp_primal_accel(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar,
                        const void* x0, double tau, double theta, double* fid, void* ws, void* stream);
 
+/* Primal step of Chambolle-Pock (Chambolle & Pock 2011, Algorithm 1; section 6.2.2 for TV-L1) for a fidelity F(x - x0) whose prox is
+ * POINTWISE, with the extrapolation folded into the same pass.  F by `fidelity`: */
+#define TV_FID_L2    0   /* 1/2 |x - x0|^2                                   */
+#define TV_FID_L1    1   /* |x - x0|_1                                       */
+#define TV_FID_HUBER 2   /* sum h_delta(x - x0): e^2/(2 delta) for |e| <= delta, |e| - delta/2 beyond */
+#define TV_CPP_RESIDUAL 1 /* flag: reduce-only */
+/* STEP mode (flags == 0), one pass of Nd + 4 words per voxel like tv_cp_primal_accel:
+ *   e = (x - tau D^T q) - x0;  x_new = x0 + prox_{tau F}(e);  x_bar = x_new + theta (x_new - x);  x = x_new;
+ *   *out (device fp64) = F(x_new - x0) over the local planes, accumulated in fp64.
+ * prox_{tau F}(e) is  e / (1 + tau)  (L2),  the soft threshold sign(e) max(|e| - tau, 0)  (L1),  e delta / (delta + tau) where
+ * |e| <= delta + tau and e - tau sign(e) beyond  (Huber).  All three are evaluated as  e - clamp(c e, -t, t)  with c = tau / (1 + tau),
+ * t = +inf (L2); c = 1, t = tau (L1); c = tau / (delta + tau), t = tau (Huber) -- constants formed once in double, no branch.  An L1 site
+ * inside the dead zone |e| <= tau therefore returns x0 BIT FOR BIT (x0 + (e - e)).  `delta` is read for Huber only.
+ * RESIDUAL mode (flags == TV_CPP_RESIDUAL): REDUCE-ONLY, nothing is written except out and ws; x_bar may be NULL and theta is ignored.
+ *   *out = sum_sites ((x - x_new) / tau)^2, accumulated site by site in fp64 -- the fixed-point residual of the fidelity block: zero iff
+ *   -D^T q is in the subdifferential of F at x - x0.  Together with tv_cp_dual_residual (zero iff q is in the subdifferential of
+ *   lambda |.|_2 at D x) it is an optimality certificate of the pair (x, q).  (A duality gap does not exist for L1 / Huber without a
+ *   feasibility projection of D^T q.)
+ * q_prev / q_next as y_prev / y_next in tv_DT; slab partials add up to the unsharded scalars.  Every geometry tv_cp_primal_accel takes, with
+ * its dispatch (four schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays -- pads stay zero --, mask_static / time_factor /
+ * time_weight_vol, z-slabs; fp32 planes of >= 4 MiB take the plane-marching kernel, both modes).
+ * TV_E_ARG: an unknown fidelity or flag bit, a NULL array (x_bar in step mode), x == x_bar, tau not finite and > 0, delta not finite and
+ * > 0 (Huber), theta not finite or outside [0, 1] (step mode); a missing halo plane is TV_E_HALO; all checks precede any device access. */
+int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar, const void* x0,
+                      int32_t fidelity, double delta, double tau, double theta, int32_t flags, double* out, void* ws, void* stream);
+
 /* Duality-gap certificate of the model every solver here minimises, P(x) = 1/2 |x - x0|^2 + lambda |D x|_{2,1}, for an iterate x and a dual
  * variable qs = qscale * q with |qs|_2 <= lambda per site (Chambolle-Pock: its q, qscale = 1; scaled-form ADMM: q = u, qscale = rho; both are
  * projections).  Over the local planes, with gd = D^T qs:

@@ -9,6 +9,7 @@
 //                AdmmZU   -> z/u update of ADMM                  (tv_admm_zu)
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
 //                StoreDT / AxpyDT / CpPrimal / CpPrimalAccel epilogues   (tv_DT, tv_DT_axpy, tv_cp_primal, tv_cp_primal_accel)
+//                CpPrimalProxT -> primal step with an L2 / L1 / Huber prox, or its reduce-only residual   (tv_cp_primal_prox)
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
 //   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
@@ -1012,6 +1013,53 @@ int tv_cp_primal_accel(const tv_geom* g, const void* q, const void* q_prev, cons
         hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalAccel<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
         HIP_TRY(hipGetLastError());
         return P.reduce(0, lc.nblocks, fid, st);
+    });
+}
+
+// Chambolle-Pock primal step with a pointwise prox of the fidelity (L2 / L1 / Huber), or its reduce-only fixed-point residual
+// (include/pytv4d.h): tv_cp_primal_accel's gather and launch rules with the CpPrimalProxT epilogue.  The prox constants are formed here in
+// double; every argument check precedes the first device access.
+int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar, const void* x0,
+                      int32_t fidelity, double delta, double tau, double theta, int32_t flags, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (fidelity != TV_FID_L2 && fidelity != TV_FID_L1 && fidelity != TV_FID_HUBER) return fail(TV_E_ARG, "unknown fidelity");
+    if (flags & ~TV_CPP_RESIDUAL) return fail(TV_E_ARG, "unknown flag bits");
+    const bool store = !(flags & TV_CPP_RESIDUAL);
+    if (q == nullptr || x == nullptr || x0 == nullptr || out == nullptr || ws == nullptr || (store && x_bar == nullptr))
+        return fail(TV_E_ARG, "NULL array");
+    if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
+    if (fidelity == TV_FID_HUBER && (!std::isfinite(delta) || !(delta > 0.0))) return fail(TV_E_ARG, "delta must be a finite number > 0");
+    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (store && (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0))) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
+    // prox_{tau F}(e) = e - clamp(c e, -t, t);  F(e) = (|e| - a) + a^2 half_inv with a = min(|e|, cap)      (tv_stencil.h)
+    const double inf = (double)INFINITY;
+    const double c = fidelity == TV_FID_L1 ? 1.0 : tau / ((fidelity == TV_FID_HUBER ? delta : 1.0) + tau);
+    const double t = fidelity == TV_FID_L2 ? inf : tau;
+    const double cap = fidelity == TV_FID_L1 ? 0.0 : (fidelity == TV_FID_HUBER ? delta : inf);
+    const double half_inv = fidelity == TV_FID_L1 ? 0.0 : (fidelity == TV_FID_HUBER ? 0.5 / delta : 0.5);
+    const double th = store ? theta : 0.0, inv_tau = 1.0 / tau;
+    if (march_ok(g, d, vec)) {
+        long long nb;
+        if (int rc = tvm::DT_cp_primal_prox(g, d, q, q_prev, q_next, st, &nb, store, (float*)x, (float*)x_bar, (const float*)x0, (float)tau,
+                                            (float)th, (float)c, (float)t, cap, half_inv, inv_tau, P.slot(0))) return rc;
+        return P.reduce(0, nb, out, st);
+    }
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
+        auto launch = [&]<bool STORE>() {
+            CpPrimalProxT<T, V, STORE> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)c, (T)t, cap, half_inv, inv_tau, P.slot(0)};
+            hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalProxT<T, V, STORE>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
+        };
+        if (store) launch.template operator()<true>();
+        else launch.template operator()<false>();
+        HIP_TRY(hipGetLastError());
+        return P.reduce(0, lc.nblocks, out, st);
     });
 }
 

@@ -39,6 +39,13 @@ int DT_cp_primal_accel(const tv_geom* g, const DG& d, const void* q, const void*
                        float* x, float* x_bar, const float* x0, float tau, float inv_1p_tau, float theta, double* partials) {
     return launch_DT_march<CpPrimalAccel, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, inv_1p_tau, theta, partials);
 }
+int DT_cp_primal_prox(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
+                      bool store, float* x, float* x_bar, const float* x0, float tau, float theta, float c, float t, double cap,
+                      double half_inv, double inv_tau, double* partials) {
+    if (store)
+        return launch_DT_march<CpPrimalProx, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, theta, c, t, cap, half_inv, inv_tau, partials);
+    return launch_DT_march<CpPrimalProxRes, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, theta, c, t, cap, half_inv, inv_tau, partials);
+}
 int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
            const float* x, const float* x0, float qscale, double* partials) {
     return launch_DT_march<GapDT, float>(g, d, q, qp, qn, st, nb, x, x0, qscale, partials);

@@ -499,6 +499,54 @@ template <typename T, int V> struct CpPrimalAccel {
     }
 };
 
+// Chambolle-Pock primal step with a POINTWISE PROX of the fidelity F(x - x0) (Chambolle & Pock 2011, Algorithm 1 / section 6.2.2: TV-L1;
+// tv_cp_primal_prox).  With e = (x - tau D^T q) - x0 every fidelity here has  prox_{tau F}(e) = e - clamp(c e, -t, t):
+//   L1     c = 1                    t = tau      the soft threshold; inside the dead zone c e == e, so e - e == 0 and x_new == x0 bit for bit
+//   Huber  c = tau / (delta + tau)  t = tau
+//   L2     c = tau / (1 + tau)      t = +inf
+// c and t are formed by the host in double.  One multiply, one three-way median, one subtract per element; no branch.
+//   STORE:  x_new = x0 + prox(e);  x_bar = x_new + theta (x_new - x);  x = x_new;  sum F(x_new - x0)          Nd + 4 words per voxel
+//   !STORE: reduce-only -- sum ((x - x_new) / tau)^2, the fixed-point residual of the fidelity block; x, x0 read, nothing written
+// F in fp64 from a = min(|e|, cap):  (|e| - a) + a^2 half_inv   (L1: cap = 0, half_inv = 0; Huber: cap = delta, half_inv = 1 / (2 delta);
+// L2: cap = +inf, half_inv = 1/2).  Pads stay zero (r, x, x0 are zero there: e = 0, prox(0) = 0).
+__device__ __forceinline__ float  tclamp(float v, float t)   { return __builtin_amdgcn_fmed3f(v, -t, t); }
+__device__ __forceinline__ double tclamp(double v, double t) { return fmin(fmax(v, -t), t); }
+template <typename T, int V, bool STORE> struct CpPrimalProxT {
+    static constexpr bool REDUCES = true;
+    T* x;
+    T* x_bar;
+    const T* x0;
+    T tau, theta, c, t;
+    double cap, half_inv, inv_tau;
+    double* partials;
+    __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
+        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        Vec<T, V> xn, xb;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const T e = (xv.v[i] - tau * r.v[i]) - x0v.v[i];
+            xn.v[i] = x0v.v[i] + (e - tclamp(c * e, t));
+            if (STORE) {
+                xb.v[i] = xn.v[i] + theta * (xn.v[i] - xv.v[i]);
+                const double ae = fabs((double)xn.v[i] - (double)x0v.v[i]);
+                const double a = fmin(ae, cap);
+                acc += (ae - a) + a * a * half_inv;
+            } else {
+                const double d = ((double)xv.v[i] - (double)xn.v[i]) * inv_tau;
+                acc += d * d;
+            }
+        }
+        if (STORE) {
+            vstore_s<T, V>(x + off, xn);
+            vstore_s<T, V>(x_bar + off, xb);
+        }
+        return acc;
+    }
+};
+template <typename T, int V> using CpPrimalProx = CpPrimalProxT<T, V, true>;       // the <typename, int> forms launch_DT_march takes
+template <typename T, int V> using CpPrimalProxRes = CpPrimalProxT<T, V, false>;
+
 // =============================================================================================
 // duality gap of 1/2 |x - x0|^2 + lambda |D x|_{2,1} at (x, qs = qscale q), reduce-only (tv_dual_gap): with gd = D^T qs
 //   gap = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda |D x|_2 - <qs, D x> ]      both parts >= 0 site by site for |qs|_2 <= lambda

@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get("PYTV4D_LIB") or os.path.join(_HERE, "libpytv4d_hip.so
 
 SCHEMES = {"upwind": 0, "downwind": 1, "central": 2, "hybrid": 3}
 TV_F32, TV_F64 = 0, 1
+FIDELITIES = {"l2": 0, "l1": 1, "huber": 2}      # TV_FID_* of include/pytv4d.h (tv_cp_primal_prox)
+TV_CPP_RESIDUAL = 1
 
 _c_void_p = ctypes.c_void_p
 _c_double_p = ctypes.c_void_p   # device pointers to fp64 scalars are passed as raw addresses
@@ -87,6 +89,8 @@ _SIGNATURES = {
     "tv_cp_dual": (ctypes.c_int, [_G] + [_c_void_p] * 4 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_primal": (ctypes.c_int, [_G] + [_c_void_p] * 6 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_primal_accel": (ctypes.c_int, [_G] + [_c_void_p] * 6 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
+    "tv_cp_primal_prox": (ctypes.c_int, [_G] + [_c_void_p] * 6 + [ctypes.c_int32] + [ctypes.c_double] * 3
+                          + [ctypes.c_int32, _c_double_p, _c_void_p, _c_void_p]),
     "tv_dual_gap": (ctypes.c_int, [_G] + [_c_void_p] * 7 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_dual_residual": (ctypes.c_int, [_G] + [_c_void_p] * 4 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_fused_supported": (ctypes.c_int, [_G]),

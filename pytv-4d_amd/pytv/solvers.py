@@ -24,13 +24,15 @@ hidden behind the interior planes' kernel.  Scalars (TV, fidelity, CG dots) stay
 fp64 and are all-reduced there; nothing synchronises with the host inside the loop.
 """
 
+import math
+
 import torch
 
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "accel_schedule",
-           "auto_pitch", "operator_norm_sq"]
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+           "accel_schedule", "auto_pitch", "operator_norm_sq"]
 
 
 def cp_step_size(nz_global, m, reg_z_over_reg, reg_time, time_weight_max=1.0):
@@ -50,6 +52,25 @@ def normal_spectral_bound(scheme, nz_global, m, reg_z_over_reg, reg_time, time_w
     t = m > 1 and reg_time > 0
     s = 2.0 + (reg_z_over_reg if z else 0.0) + (reg_time * time_weight_max if t else 0.0)
     return (1.0 if scheme == "central" else 4.0) * s
+
+
+def cp_step_pair(L2, tau=None, sigma=None, names=("tau", "sigma")):
+    """(tau, sigma) of a primal-dual iteration whose convergence wants tau sigma L^2 <= 1 (``L2`` = ``normal_spectral_bound``) as Python
+    floats.  Both None: 1 / sqrt(L^2) each; one given: the other is 1 / (L^2 times it).  ValueError unless both are finite and > 0 and
+    tau sigma L^2 <= 1 + 1e-12; ``names``: what the caller's parameters are called, for the messages."""
+    if tau is None and sigma is None:
+        tau = sigma = 1.0 / math.sqrt(L2)
+    elif tau is None:
+        tau = 1.0 / (L2 * float(sigma)) if float(sigma) != 0.0 else 0.0      # (0 is refused below, not by the division)
+    elif sigma is None:
+        sigma = 1.0 / (L2 * float(tau)) if float(tau) != 0.0 else 0.0
+    tau, sigma = float(tau), float(sigma)
+    if not (tau > 0.0 and sigma > 0.0 and math.isfinite(tau + sigma)):
+        raise ValueError("%s and %s must be finite and > 0" % tuple(names))
+    if tau * sigma * L2 > 1.0 + 1e-12:
+        raise ValueError("%s * %s * L^2 = %.6g > 1 (L^2 = %g: normal_spectral_bound): the iteration need not converge"
+                         % (names[0], names[1], tau * sigma * L2, L2))
+    return tau, sigma
 
 
 def accel_schedule(tau0, sigma0, gamma, n, start=0):
@@ -285,6 +306,21 @@ class _SlabProblem:
             return self.geo.new_image(n)
         return torch.empty((n, m, ny, nx), dtype=self.dtype, device=self.device)
 
+    # ---- buffers of the Chambolle-Pock loops: one boundary plane of x and of q per neighbour that the scheme reads -----------------------
+    def _halo_set(self):
+        """A set of halo planes of its own: dict(xp, xn, qp, qn), None where ``plan`` needs no plane (the loop's set is bound by
+        ``_bind_loop_buffers``; a check that must leave those alone takes a second one)."""
+        pl = self.plan
+        return dict(xp=self.new_plane() if pl.x_need_prev else None, xn=self.new_plane() if pl.x_need_next else None,
+                    qp=self.new_plane() if pl.g_need_prev else None, qn=self.new_plane() if pl.g_need_next else None)
+
+    def _bind_loop_buffers(self):
+        """``ws`` (the kernels' workspace), ``plan`` (which planes travel) and the loop's halo planes ``xh_prev / xh_next / qh_prev / qh_next``"""
+        self.ws = self.geo.workspace()
+        self.plan = HaloPlan(self.slab, self.scheme, self.geo.z_active)
+        h = self._halo_set()
+        self.xh_prev, self.xh_next, self.qh_prev, self.qh_next = h["xp"], h["xn"], h["qp"], h["qn"]
+
     # ---- the arena (round 5, OPT-IN): ONE allocation for the arrays an iteration streams through ---------------------------------------
     # The time of the streaming kernels depends on where their arrays sit in physical memory (EXPERIMENTS.md section 3, round 4: the
     # "placement lottery" -- separate allocations land anywhere: 31.3 - 34.2 ms per north-star sweep from one construction to the next).
@@ -482,9 +518,7 @@ class _SlabProblem:
         pl, s = self.plan, self.slab
         b = getattr(self, "_gap_buf", None)
         if b is None:
-            b = self._gap_buf = dict(out=torch.zeros(3, dtype=torch.float64, device=self.device),
-                                     xp=self.new_plane() if pl.x_need_prev else None, xn=self.new_plane() if pl.x_need_next else None,
-                                     qp=self.new_plane() if pl.g_need_prev else None, qn=self.new_plane() if pl.g_need_next else None)
+            b = self._gap_buf = dict(out=torch.zeros(3, dtype=torch.float64, device=self.device), **self._halo_set())
         s.wait(pl.exchange_image(x, b["xp"], b["xn"]))
         s.wait(pl.exchange_grad(q, _plane0(b["qp"]), _plane0(b["qn"])))
         out = b["out"]
@@ -632,15 +666,10 @@ class ChambollePock(_SlabProblem):
         self._x0_src, self._q_pingpong, self._arena_want = self.x0, bool(q_pingpong), arena
         self.arena = False
         self._alloc_state()
-        self.ws = self.geo.workspace()
-        self.plan = HaloPlan(self.slab, scheme, self.geo.z_active)
+        self._bind_loop_buffers()
         pl = self.plan
         sh = pl.on
         self.ch_back, self.ch_fwd = pl.ch_back, pl.ch_fwd
-        self.xh_prev = self.new_plane() if pl.x_need_prev else None
-        self.xh_next = self.new_plane() if pl.x_need_next else None
-        self.qh_prev = self.new_plane() if pl.g_need_prev else None
-        self.qh_next = self.new_plane() if pl.g_need_next else None
         self.overlap = bool(overlap) and sh and self.slab.nz >= 3 and not self.fused
         self.hist = None
         self.it = 0
@@ -1100,7 +1129,67 @@ class ChambollePock(_SlabProblem):
 
 
 # =================================================================================================
-class AcceleratedChambollePock(_SlabProblem):
+class _ExtrapolatedCP(_SlabProblem):
+    """What the Chambolle-Pock solvers with the state (x, x_bar, q) share (``AcceleratedChambollePock``, ``RobustChambollePock``): the state
+    and its halo planes, the dual half of an iteration -- tv_cp_dual on the extrapolated point x_bar -- and the loop around ``step``.  A
+    subclass validates its steps (``cp_step_pair`` on ``L2``), calls ``_alloc_state`` and supplies ``step``: ``_dual_half`` + its primal
+    kernel.  Per-step scalars: the slots of ``ChambollePock``."""
+
+    SLOTS, F = ChambollePock.SLOTS, ChambollePock.F
+    loss_from_slots = ChambollePock.loss_from_slots
+
+    def __init__(self, x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch):
+        super().__init__(x0, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch=pitch)
+        self.reg = float(regularization)
+        self.L2 = normal_spectral_bound(scheme, self.slab.nz_global, x0.shape[1], reg_z_over_reg, reg_time, self.geo.time_weight_max)
+
+    def _alloc_state(self):
+        """x = x_bar = x0, q = 0, the loop's buffers, iteration 0.  (The order of the allocations is kept as it was measured: where
+        separate allocations land moves the streaming kernels' time, see the arena comment in ``_SlabProblem``.)"""
+        self.x = self.image_copy(self.x0)
+        self.x_bar = self.image_copy(self.x0)
+        self.q = self.new_grad()
+        self._bind_loop_buffers()
+        self.it = 0
+        self._scratch = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        """Back to the state of a fresh solver: x = x_bar = x0, q = 0, iteration 0 (where the steps follow a schedule, it starts again).
+        Choices made after construction (``AcceleratedChambollePock.set_fused``) stay."""
+        self.x.copy_(self.x0)
+        self.x_bar.copy_(self.x0)
+        self.q.zero_()
+        self.it = 0
+
+    def _dual_half(self, sigma, out):
+        """q <- proj_{|.|_2 <= reg}(q + sigma D x_bar), this rank's |D x_bar|_{2,1} into out[0]; sharded: the boundary planes of x_bar travel
+        before the kernel and those of the new q after it (into ``qh_prev`` / ``qh_next``, for the primal kernel), both waits exposed."""
+        s, pl = self.slab, self.plan
+        if pl.on:           # (no plane travels otherwise: at launch-bound sizes the two empty exchanges are host time worth skipping)
+            s.wait(pl.exchange_image(self.x_bar, self.xh_prev, self.xh_next))
+        _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
+                                      sigma, self.reg, out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))
+        if pl.on:
+            s.wait(pl.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next)))
+
+    def run_steps(self, rows):
+        """Enqueue ``len(rows)`` iterations, row k of the (n, SLOTS) fp64 device tensor ``rows`` (zero on entry) receiving the scalars of
+        iteration k."""
+        for k in range(rows.shape[0]):
+            self.step(rows[k])
+
+    def _run(self, n_iter, record_loss):
+        """``run`` of the subclasses (each documents what its loss history means)"""
+        hist = torch.zeros((int(n_iter), self.SLOTS), dtype=torch.float64, device=self.device)
+        self.run_steps(hist)
+        if not record_loss:
+            return None
+        self.slab.allreduce_sum_(hist)
+        return self.loss_from_slots(hist.cpu().numpy(), self.reg)
+
+
+# =================================================================================================
+class AcceleratedChambollePock(_ExtrapolatedCP):
     """min_x 1/2 |x - x0|^2 + regularization * TV(x) with the ACCELERATED primal-dual iteration (Chambolle & Pock 2011, Algorithm 2).
     The fidelity is 1-strongly convex: with theta_k = 1 / sqrt(1 + 2 gamma tau_k), tau_{k+1} = theta_k tau_k, sigma_{k+1} = sigma_k / theta_k
     (``accel_schedule``; gamma <= 1) the iterates converge as O(1/k^2) where ``ChambollePock`` -- the reference's README loop, fixed steps,
@@ -1131,48 +1220,18 @@ class AcceleratedChambollePock(_SlabProblem):
     Per-step scalars: the slots of ``ChambollePock`` -- TV in slot 0, fidelity in slot ``F`` (one-sweep path: the sweep's part in slot ``F``,
     the fix-up's in ``F + 1``; they are summed when the loss is asked for)."""
 
-    SLOTS = ChambollePock.SLOTS
-    F = ChambollePock.F
-
-    @classmethod
-    def loss_from_slots(cls, h, regularization):
-        """loss history from an (n, SLOTS) array of (already rank-summed) per-step scalars (``run``)"""
-        return h[:, cls.F:cls.SLOTS].sum(axis=1) + regularization * h[:, 0:cls.F].sum(axis=1)
-
     def __init__(self, x0, regularization, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
                  factor_reg_static=0, tau0=None, sigma0=None, gamma=1.0, slab=None, pitch="auto"):
         """tau0, sigma0: the steps of iteration 0; they must satisfy tau0 sigma0 L^2 <= 1 with L^2 = ``normal_spectral_bound`` of the geometry
         (the time axis weighted by the largest per-pixel weight, as in ``cp_step_size``), else ValueError.  Default: both 1 / sqrt(L^2); one
         given: the other is 1 / (L^2 times it).  gamma: the strong-convexity constant the schedule uses, 1.0 = that of the fidelity term
         (0 <= gamma <= 1 keeps the O(1/k^2) proof; 0 = constant steps).  pitch: see ``_SlabProblem``."""
-        import math
-        super().__init__(x0, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch=pitch)
-        self.reg = float(regularization)
-        self.L2 = normal_spectral_bound(scheme, self.slab.nz_global, x0.shape[1], reg_z_over_reg, reg_time, self.geo.time_weight_max)
-        if tau0 is None and sigma0 is None:
-            tau0 = sigma0 = 1.0 / math.sqrt(self.L2)
-        elif tau0 is None:
-            tau0 = 1.0 / (self.L2 * float(sigma0))
-        elif sigma0 is None:
-            sigma0 = 1.0 / (self.L2 * float(tau0))
-        self.tau0, self.sigma0, self.gamma = float(tau0), float(sigma0), float(gamma)
-        if not (self.tau0 > 0.0 and self.sigma0 > 0.0 and self.gamma >= 0.0 and math.isfinite(self.tau0 + self.sigma0 + self.gamma)):
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
+        self.gamma = float(gamma)
+        if not (self.gamma >= 0.0 and math.isfinite(self.gamma)):
             raise ValueError("tau0 and sigma0 must be finite and > 0, gamma finite and >= 0")
-        if self.tau0 * self.sigma0 * self.L2 > 1.0 + 1e-12:
-            raise ValueError("tau0 * sigma0 * L^2 = %.6g > 1 (L^2 = %g: normal_spectral_bound): the iteration need not converge"
-                             % (self.tau0 * self.sigma0 * self.L2, self.L2))
-        self.x = self.image_copy(self.x0)
-        self.x_bar = self.image_copy(self.x0)
-        self.q = self.new_grad()
-        self.ws = self.geo.workspace()
-        self.plan = HaloPlan(self.slab, scheme, self.geo.z_active)
-        pl = self.plan
-        self.xh_prev = self.new_plane() if pl.x_need_prev else None
-        self.xh_next = self.new_plane() if pl.x_need_next else None
-        self.qh_prev = self.new_plane() if pl.g_need_prev else None
-        self.qh_next = self.new_plane() if pl.g_need_next else None
-        self.it = 0
-        self._scratch = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
+        self.tau0, self.sigma0 = cp_step_pair(self.L2, tau0, sigma0, names=("tau0", "sigma0"))
+        self._alloc_state()
         self._sched = None
         self.x_bar_alt = None            # ping-pong partner of x_bar on the one-sweep path, allocated on first use
         self.set_fused(None)
@@ -1206,19 +1265,12 @@ class AcceleratedChambollePock(_SlabProblem):
         tau, sigma, theta = self._sched[1]
         return float(tau[k]), float(sigma[k]), float(theta[k])
 
-    def reset(self):
-        """Back to the state of a fresh solver: x = x_bar = x0, q = 0, and the step schedule at iteration 0.  The path (``fused``) stays."""
-        self.x.copy_(self.x0)
-        self.x_bar.copy_(self.x0)
-        self.q.zero_()
-        self.it = 0
-
     def step(self, out=None):
         """Enqueue one iteration with the steps of iteration ``self.it``.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this
         rank's |D x_bar|_{2,1} in slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch."""
         out = self._scratch if out is None else out
         tau, sigma, theta = self._steps(self.it)
-        s, pl, F = self.slab, self.plan, self.F
+        F = self.F
         if self._fused:
             # one sweep over all chunks (x_bar -> x_bar_alt, x and q in place), one fix-up over all planes; both return a part of the fidelity
             if self.x_bar_alt is None:
@@ -1232,20 +1284,11 @@ class AcceleratedChambollePock(_SlabProblem):
             self.x_bar, self.x_bar_alt = self.x_bar_alt, self.x_bar
             self.it += 1
             return
-        s.wait(pl.exchange_image(self.x_bar, self.xh_prev, self.xh_next))
-        _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
-                                      sigma, self.reg, out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))
-        s.wait(pl.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next)))
+        self._dual_half(sigma, out)
         _nv.check(self.lib.tv_cp_primal_accel(self.geo.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x),
                                               _nv.ptr(self.x_bar), _nv.ptr(self.x0), tau, theta, out[F:F + 1].data_ptr(), _nv.ptr(self.ws),
                                               self.stream))
         self.it += 1
-
-    def run_steps(self, rows):
-        """Enqueue ``len(rows)`` iterations, row k of the (n, SLOTS) fp64 device tensor ``rows`` (zero on entry) receiving the scalars of
-        iteration k."""
-        for k in range(rows.shape[0]):
-            self.step(rows[k])
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
@@ -1253,12 +1296,7 @@ class AcceleratedChambollePock(_SlabProblem):
         of an iterate -- a progress indicator in the slots of ``ChambollePock``'s history, not the objective of x_{k+1}.  The exact primal
         value of the current iterate is ``duality_gap()[0]``.  A diverging run (steps forced past the bound) returns its numbers, non-finite
         ones included; it never raises."""
-        hist = torch.zeros((int(n_iter), self.SLOTS), dtype=torch.float64, device=self.device)
-        self.run_steps(hist)
-        if not record_loss:
-            return None
-        self.slab.allreduce_sum_(hist)
-        return self.loss_from_slots(hist.cpu().numpy(), self.reg)
+        return self._run(n_iter, record_loss)
 
     def duality_gap(self):
         """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
@@ -1277,7 +1315,7 @@ class AcceleratedChambollePock(_SlabProblem):
 
 
 # =================================================================================================
-class RobustChambollePock(_SlabProblem):
+class RobustChambollePock(_ExtrapolatedCP):
     """min_x F(x - x0) + regularization * TV(x) for a ROBUST data term F (Chambolle & Pock 2011, section 6.2.2: TV-L1), with Algorithm 1
     of that paper (theta = 1, fixed steps).  ``fidelity``:
 
@@ -1309,66 +1347,25 @@ class RobustChambollePock(_SlabProblem):
 
     Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, F(x_new - x0) in slot ``F``."""
 
-    SLOTS = ChambollePock.SLOTS
-    F = ChambollePock.F
-
-    @classmethod
-    def loss_from_slots(cls, h, regularization):
-        """loss history from an (n, SLOTS) array of (already rank-summed) per-step scalars (``run``)"""
-        return h[:, cls.F:cls.SLOTS].sum(axis=1) + regularization * h[:, 0:cls.F].sum(axis=1)
-
     def __init__(self, x0, regularization, fidelity="l1", delta=None, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
                  factor_reg_static=0, tau=None, sigma=None, slab=None, pitch="auto"):
         """fidelity: "l1", "huber" or "l2"; delta: the Huber width in grey levels (required for "huber", ignored otherwise).  tau, sigma: see
         the class docstring -- tau * sigma * L^2 > 1 + 1e-12 raises ValueError.  pitch: see ``_SlabProblem``."""
-        import math
         if fidelity not in _nv.FIDELITIES:
             raise ValueError("fidelity must be one of %s, got %r" % (sorted(_nv.FIDELITIES), fidelity))
         if fidelity == "huber":
             if delta is None or not (float(delta) > 0.0 and math.isfinite(float(delta))):
                 raise ValueError("fidelity='huber' needs a finite delta > 0")
-        super().__init__(x0, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch=pitch)
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
         self.fidelity, self.fid_code = fidelity, _nv.FIDELITIES[fidelity]
         self.delta = float(delta) if fidelity == "huber" else 0.0
-        self.reg = float(regularization)
-        self.L2 = normal_spectral_bound(scheme, self.slab.nz_global, x0.shape[1], reg_z_over_reg, reg_time, self.geo.time_weight_max)
-        if tau is None and sigma is None:
-            tau = sigma = 1.0 / math.sqrt(self.L2)
-        elif tau is None:
-            tau = 1.0 / (self.L2 * float(sigma))
-        elif sigma is None:
-            sigma = 1.0 / (self.L2 * float(tau))
-        self.tau, self.sigma = float(tau), float(sigma)
-        if not (self.tau > 0.0 and self.sigma > 0.0 and math.isfinite(self.tau + self.sigma)):
-            raise ValueError("tau and sigma must be finite and > 0")
-        if self.tau * self.sigma * self.L2 > 1.0 + 1e-12:
-            raise ValueError("tau * sigma * L^2 = %.6g > 1 (L^2 = %g: normal_spectral_bound): the iteration need not converge"
-                             % (self.tau * self.sigma * self.L2, self.L2))
-        self.x = self.image_copy(self.x0)
-        self.x_bar = self.image_copy(self.x0)
-        self.q = self.new_grad()
-        self.ws = self.geo.workspace()
-        self.plan = HaloPlan(self.slab, scheme, self.geo.z_active)
-        pl = self.plan
-        self.xh_prev = self.new_plane() if pl.x_need_prev else None
-        self.xh_next = self.new_plane() if pl.x_need_next else None
-        self.qh_prev = self.new_plane() if pl.g_need_prev else None
-        self.qh_next = self.new_plane() if pl.g_need_next else None
-        self.it = 0
-        self._scratch = torch.zeros(self.SLOTS, dtype=torch.float64, device=self.device)
+        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        self._alloc_state()
         # halo buffers of ``residuals`` (its own: the loop's are not touched), and R_0 of the starting pair, enqueued here and read back
         # (one synchronisation) only when somebody asks
-        self._res_buf = dict(xp=self.new_plane() if pl.x_need_prev else None, xn=self.new_plane() if pl.x_need_next else None,
-                             qp=self.new_plane() if pl.g_need_prev else None, qn=self.new_plane() if pl.g_need_next else None)
+        self._res_buf = self._halo_set()
         self._res0 = self._residual_scalars()
         self._R0 = None
-
-    def reset(self):
-        """Back to the state of a fresh solver: x = x_bar = x0, q = 0."""
-        self.x.copy_(self.x0)
-        self.x_bar.copy_(self.x0)
-        self.q.zero_()
-        self.it = 0
 
     def _prox(self, q, qp, qn, x, x_bar, theta, flags, out_ptr):
         _nv.check(self.lib.tv_cp_primal_prox(self.geo.ref, _nv.ptr(q), _nv.ptr(qp), _nv.ptr(qn), _nv.ptr(x), _nv.ptr(x_bar), _nv.ptr(self.x0),
@@ -1378,31 +1375,16 @@ class RobustChambollePock(_SlabProblem):
         """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
         F(x_new - x0) in slot F; defaults to an internal scratch."""
         out = self._scratch if out is None else out
-        s, pl, F = self.slab, self.plan, self.F
-        s.wait(pl.exchange_image(self.x_bar, self.xh_prev, self.xh_next))
-        _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
-                                      self.sigma, self.reg, out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))
-        s.wait(pl.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next)))
-        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[F:F + 1].data_ptr())
+        self._dual_half(self.sigma, out)
+        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[self.F:self.F + 1].data_ptr())
         self.it += 1
-
-    def run_steps(self, rows):
-        """Enqueue ``len(rows)`` iterations, row k of the (n, SLOTS) fp64 device tensor ``rows`` (zero on entry) receiving the scalars of
-        iteration k."""
-        for k in range(rows.shape[0]):
-            self.step(rows[k])
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
         None.  Row k is F(x_{k+1} - x0) + reg |D x_bar_k|_{2,1}: the TV term is that of the extrapolated point the dual step saw -- a
         progress indicator in the slots of ``ChambollePock``'s history; the objective of the current iterate is
         ``residuals()["fid"] + reg * residuals()["tv"]``."""
-        hist = torch.zeros((int(n_iter), self.SLOTS), dtype=torch.float64, device=self.device)
-        self.run_steps(hist)
-        if not record_loss:
-            return None
-        self.slab.allreduce_sum_(hist)
-        return self.loss_from_slots(hist.cpu().numpy(), self.reg)
+        return self._run(n_iter, record_loss)
 
     # ---- optimality residual of the saddle problem (tv_cp_dual_residual + tv_cp_primal_prox in residual mode) ----------------------------
     _RES_DOC = """(x, q) is a saddle point of  min_x max_{|q|_2 <= reg}  F(x - x0) + <D x, q>  (whose x solves the problem) iff it is a fixed point
@@ -1517,14 +1499,9 @@ class ChambollePockOperator(_SlabProblem):
         self.b = b.to(self.dtype).contiguous()
         self.p = torch.zeros_like(self.b)
         self.q = torch.zeros(self.geo.grad_shape, dtype=self.dtype, device=self.device)
-        self.ws = self.geo.workspace()
+        self.ws = self.geo.workspace()              # allocated before x_new, as it always was (``_bind_loop_buffers`` binds the same one)
         self.x_new = torch.empty_like(self.x)
-        self.plan = HaloPlan(self.slab, scheme, self.geo.z_active)
-        pl = self.plan
-        self.xh_prev = self.new_plane() if pl.x_need_prev else None
-        self.xh_next = self.new_plane() if pl.x_need_next else None
-        self.qh_prev = self.new_plane() if pl.g_need_prev else None
-        self.qh_next = self.new_plane() if pl.g_need_next else None
+        self._bind_loop_buffers()
         # the residual r = A x - b is CARRIED from one iteration to the next (round 2 applied A twice per iteration: once
         # for the dual update, once more for the loss of the new iterate -- the next iteration's first residual)
         self.r = torch.empty_like(self.b)
@@ -1617,8 +1594,8 @@ class ChambollePockOperator(_SlabProblem):
         self._steps += 1
 
     def run(self, n_iter):
-        hist = torch.zeros((n_iter, 2), dtype=torch.float64, device=self.device)
-        for it in range(n_iter):
+        hist = torch.zeros((int(n_iter), 2), dtype=torch.float64, device=self.device)
+        for it in range(hist.shape[0]):
             self.step(hist[it])
         self.slab.allreduce_sum_(hist)
         h = hist.cpu().numpy()

@@ -221,6 +221,29 @@ int tv_cp_primal_accel(const tv_geom* g, const void* q, const void* q_prev, cons
 int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar, const void* x0,
                       int32_t fidelity, double delta, double tau, double theta, int32_t flags, double* out, void* ws, void* stream);
 
+/* Primal step of Chambolle-Pock (Chambolle & Pock 2011, Algorithm 1) for the POISSON data term: the generalised Kullback-Leibler divergence
+ *   F(x) = sum_sites ( x - x0 + x0 log(x0 / x) )  over x >= 0, for counts x0 >= 0  (0 log 0 = 0; +inf where x = 0 < x0),
+ * with the extrapolation folded into the same pass.  flags: 0 or TV_CPP_RESIDUAL.
+ * STEP mode (flags == 0), one pass of Nd + 4 words per voxel like tv_cp_primal_prox:
+ *   v = x - tau D^T q;  b = v - tau;  s = sqrt(b^2 + 4 tau x0);
+ *   x_new = prox_{tau F}(v) = (b + s) / 2, evaluated as  b >= 0 ? (b + s) / 2 : 2 tau x0 / (s - b)  -- the same root without the
+ *   cancellation of b + s for b << 0;  x_bar = x_new + theta (x_new - x);  x = x_new;
+ *   *out (device fp64) = F(x_new) over the local planes, accumulated in fp64.
+ * A site with x0 == 0 returns exactly 0 for b < 0 and b otherwise; x_new >= 0 everywhere.  x0 >= 0 is the caller's contract: the kernel does
+ * not clamp it (a negative x0 can give NaN).
+ * RESIDUAL mode (flags == TV_CPP_RESIDUAL): REDUCE-ONLY, nothing is written except out and ws; x_bar may be NULL and theta is ignored.
+ *   *out = sum_sites ((x - x_new) / tau)^2 in fp64 -- zero iff -D^T q is in the subdifferential of F at x; with tv_cp_dual_residual an
+ *   optimality certificate of the pair (x, q).
+ *   Where x + tau (1 + D^T q) >= 0 the displacement is evaluated as 2 (x0 - x (1 + D^T q)) / (s + x + tau (1 + D^T q)), the same number in
+ *   exact arithmetic: an exact 0 at x = x0, D^T q = 0 (a constant image), and equal to (x - x_new) / tau to rounding elsewhere.
+ * q_prev / q_next, geometries and dispatch as tv_cp_primal_prox (four schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays --
+ * pads stay zero --, mask_static / time_factor / time_weight_vol, z-slabs; fp32 planes of >= 4 MiB take the plane-marching kernel, both
+ * modes); slab partials add up to the unsharded scalars.
+ * TV_E_ARG: an unknown flag bit, a NULL array (x_bar in step mode), x == x_bar, tau not finite and > 0, theta not finite or outside [0, 1]
+ * (step mode); a missing halo plane is TV_E_HALO; all checks precede any device access. */
+int tv_cp_primal_kl(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar,
+                    const void* x0, double tau, double theta, int32_t flags, double* out, void* ws, void* stream);
+
 /* Duality-gap certificate of the model every solver here minimises, P(x) = 1/2 |x - x0|^2 + lambda |D x|_{2,1}, for an iterate x and a dual
  * variable qs = qscale * q with |qs|_2 <= lambda per site (Chambolle-Pock: its q, qscale = 1; scaled-form ADMM: q = u, qscale = rho; both are
  * projections).  Over the local planes, with gd = D^T qs:

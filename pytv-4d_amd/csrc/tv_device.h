@@ -43,6 +43,9 @@ template <> struct Consts<double> { static __device__ __forceinline__ double inv
 // IEEE-correct sqrt (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt keeps it so) and max
 __device__ __forceinline__ float  tsqrt(float v)  { return __fsqrt_rn(v); }
 __device__ __forceinline__ double tsqrt(double v) { return __dsqrt_rn(v); }
+// one rounding, spelled out where the rounding matters (tv_fused.h: the norm chains; tv_stencil.h: the Kullback-Leibler prox)
+__device__ __forceinline__ float  tfma(float a, float b, float c)    { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double tfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float  tmax(float a, float b)   { return fmaxf(a, b); }
 __device__ __forceinline__ double tmax(double a, double b) { return fmax(a, b); }
 

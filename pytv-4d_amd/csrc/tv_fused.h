@@ -299,8 +299,7 @@ template <typename T, int V> __device__ __forceinline__ Vec<T, V> cp_shfl_down(c
 // per further slot.  Written as `s + o * o` (sumsq_slots) the first two terms are fadd(fmul, fmul), which the compiler may contract either
 // way round, and two instantiations of this kernel did: *tv of the ALG_CPACC sweep differed from the ALG_CP one's in the 11th digit on
 // the same input (hybrid, 2 frames, fp32).  NS: slots the scheme uses (the others are exactly zero); an inactive axis adds fma(0, 0, s) = s.
-__device__ __forceinline__ float tfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double tfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// (tfma: tv_device.h)
 template <int NS, typename T, int V> __device__ __forceinline__ Vec<T, V> sumsq_slots_pinned(const Vec<T, V> (&o)[8]) {
     Vec<T, V> s;
 #pragma unroll

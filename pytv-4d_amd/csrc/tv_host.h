@@ -359,6 +359,10 @@ int DT_cp_primal_accel(const tv_geom* g, const DG& d, const void* q, const void*
 int DT_cp_primal_prox(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
                       bool store, float* x, float* x_bar, const float* x0, float tau, float theta, float c, float t, double cap,
                       double half_inv, double inv_tau, double* partials);
+// primal step for the Poisson / Kullback-Leibler data term (tv_cp_primal_kl; CpPrimalKLT of tv_stencil.h): store / !store as above
+int DT_cp_primal_kl(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
+                    bool store, float* x, float* x_bar, const float* x0, float tau, float theta, float two_tau, float four_tau,
+                    double inv_tau, double* partials);
 // duality gap, reduce-only (tv_dual_gap): the D^T-side pass writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2, the D-side pass (same
 // grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to the first pass's sums
 int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,

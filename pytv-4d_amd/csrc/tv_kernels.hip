@@ -10,6 +10,7 @@
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
 //                StoreDT / AxpyDT / CpPrimal / CpPrimalAccel epilogues   (tv_DT, tv_DT_axpy, tv_cp_primal, tv_cp_primal_accel)
 //                CpPrimalProxT -> primal step with an L2 / L1 / Huber prox, or its reduce-only residual   (tv_cp_primal_prox)
+//                CpPrimalKLT   -> primal step with the Poisson / Kullback-Leibler prox, or its residual     (tv_cp_primal_kl)
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
 //   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
@@ -1055,6 +1056,44 @@ int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const
         auto launch = [&]<bool STORE>() {
             CpPrimalProxT<T, V, STORE> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)c, (T)t, cap, half_inv, inv_tau, P.slot(0)};
             hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalProxT<T, V, STORE>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
+        };
+        if (store) launch.template operator()<true>();
+        else launch.template operator()<false>();
+        HIP_TRY(hipGetLastError());
+        return P.reduce(0, lc.nblocks, out, st);
+    });
+}
+
+// Chambolle-Pock primal step for the Poisson / Kullback-Leibler data term, or its reduce-only fixed-point residual (include/pytv4d.h):
+// tv_cp_primal_prox's checks, gather and launch rules with the CpPrimalKLT epilogue.  2 tau and 4 tau are formed here in double.
+int tv_cp_primal_kl(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar, const void* x0,
+                    double tau, double theta, int32_t flags, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (flags & ~TV_CPP_RESIDUAL) return fail(TV_E_ARG, "unknown flag bits");
+    const bool store = !(flags & TV_CPP_RESIDUAL);
+    if (q == nullptr || x == nullptr || x0 == nullptr || out == nullptr || ws == nullptr || (store && x_bar == nullptr))
+        return fail(TV_E_ARG, "NULL array");
+    if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
+    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (store && (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0))) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
+    const double th = store ? theta : 0.0, two_tau = 2.0 * tau, four_tau = 4.0 * tau, inv_tau = 1.0 / tau;
+    if (march_ok(g, d, vec)) {
+        long long nb;
+        if (int rc = tvm::DT_cp_primal_kl(g, d, q, q_prev, q_next, st, &nb, store, (float*)x, (float*)x_bar, (const float*)x0, (float)tau,
+                                          (float)th, (float)two_tau, (float)four_tau, inv_tau, P.slot(0))) return rc;
+        return P.reduce(0, nb, out, st);
+    }
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
+        auto launch = [&]<bool STORE>() {
+            CpPrimalKLT<T, V, STORE> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)two_tau, (T)four_tau, inv_tau, P.slot(0)};
+            hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalKLT<T, V, STORE>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
         };
         if (store) launch.template operator()<true>();
         else launch.template operator()<false>();

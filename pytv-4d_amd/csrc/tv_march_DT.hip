@@ -46,6 +46,13 @@ int DT_cp_primal_prox(const tv_geom* g, const DG& d, const void* q, const void* 
         return launch_DT_march<CpPrimalProx, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, theta, c, t, cap, half_inv, inv_tau, partials);
     return launch_DT_march<CpPrimalProxRes, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, theta, c, t, cap, half_inv, inv_tau, partials);
 }
+int DT_cp_primal_kl(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
+                    bool store, float* x, float* x_bar, const float* x0, float tau, float theta, float two_tau, float four_tau,
+                    double inv_tau, double* partials) {
+    if (store)
+        return launch_DT_march<CpPrimalKL, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, theta, two_tau, four_tau, inv_tau, partials);
+    return launch_DT_march<CpPrimalKLRes, float>(g, d, q, qp, qn, st, nb, x, x_bar, x0, tau, theta, two_tau, four_tau, inv_tau, partials);
+}
 int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
            const float* x, const float* x0, float qscale, double* partials) {
     return launch_DT_march<GapDT, float>(g, d, q, qp, qn, st, nb, x, x0, qscale, partials);

@@ -547,6 +547,68 @@ template <typename T, int V, bool STORE> struct CpPrimalProxT {
 template <typename T, int V> using CpPrimalProx = CpPrimalProxT<T, V, true>;       // the <typename, int> forms launch_DT_march takes
 template <typename T, int V> using CpPrimalProxRes = CpPrimalProxT<T, V, false>;
 
+// Chambolle-Pock primal step for the POISSON data term, the generalised Kullback-Leibler divergence F(x) = sum (x - x0 + x0 log(x0 / x)) over
+// x >= 0 with counts x0 >= 0 (0 log 0 = 0; tv_cp_primal_kl).  With v = x - tau D^T q and b = v - tau the prox is the positive root of
+// x^2 - b x - tau x0:  prox_{tau F}(v) = (b + s) / 2,  s = sqrt(b^2 + 4 tau x0).  For b << 0 that sum cancels to nothing, so the root is taken
+// in the form that adds magnitudes on either side of b = 0 (the two are the same number: (b + s)(s - b) = 4 tau x0):
+//   x_new = b >= 0 ? (b + s) / 2 : 2 tau x0 / (s - b)                         a select; both arms are evaluated
+// two_tau and four_tau are formed by the host in double.  Exact by construction: x0 = 0 with b < 0 gives 0 / (2 |b|) = 0 (x0 = 0 with b >= 0
+// gives b), and a pad element (r = x = x0 = 0, so b = -tau) stays 0 however the square root rounds.  x0 >= 0 is the caller's contract.
+//   STORE:  x_bar = x_new + theta (x_new - x);  x = x_new;  sum F(x_new) in fp64                              Nd + 4 words per voxel
+//   !STORE: reduce-only -- sum ((x - x_new) / tau)^2, the fixed-point residual of the fidelity block; x, x0 read, nothing written.  Exactly
+//           0 at a site that is a fixed point in exact arithmetic with representable data (see below), which x - x_new need not be.
+__device__ __forceinline__ float  tlog1p(float v)  { return log1pf(v); }
+__device__ __forceinline__ double tlog1p(double v) { return log1p(v); }
+// one site of F: x - x0 + x0 log(x0 / x) = x0 (u - log1p(u)) with u = (x - x0) / x0, evaluated in T (>= 0 term by term: u >= log1p(u)) and
+// accumulated in fp64 by the caller; x where x0 == 0.  (A double-precision log per voxel showed through the memory traffic: DESIGN.md 3.6.)
+template <typename T> __device__ __forceinline__ double kl_term(T xn, T x0) {
+    const T u = (xn - x0) / x0;
+    return (double)(x0 > T(0) ? x0 * (u - tlog1p(u)) : xn);
+}
+template <typename T, int V, bool STORE> struct CpPrimalKLT {
+    static constexpr bool REDUCES = true;
+    T* x;
+    T* x_bar;
+    const T* x0;
+    T tau, theta, two_tau, four_tau;
+    double inv_tau;
+    double* partials;
+    __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
+        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        Vec<T, V> xn, xb;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const T b = (xv.v[i] - tau * r.v[i]) - tau;
+            const T s = tsqrt(tfma(b, b, four_tau * x0v.v[i]));
+            const T hi = T(0.5) * (b + s), lo = (two_tau * x0v.v[i]) / (s - b);
+            xn.v[i] = b >= T(0) ? hi : lo;
+            if (STORE) {
+                xb.v[i] = xn.v[i] + theta * (xn.v[i] - xv.v[i]);
+                acc += kl_term(xn.v[i], x0v.v[i]);
+            } else {
+                // x_new - x = (s - c) / 2 with c = 2 x - b = x + tau (1 + r), and s^2 - c^2 = 4 tau (x0 - x (1 + r)): for c >= 0 the
+                // displacement is taken from that numerator, which is an exact 0 at a fixed point (x = x0, r = 0: a constant image).
+                // The numerator is rounded in T: near a fixed point that is not exactly one it cancels, and (x_new - x) / tau carries
+                // about 2 eps (x0 + |x| |1 + r|) / (s + c) per site -- bounded by the eps |x| / tau that x - x_new carries, so the sum
+                // equals sum ((x - x_new) / tau)^2 to rounding, not bit for bit.
+                const T c = (xv.v[i] + tau * r.v[i]) + tau;
+                const double den = (double)s + (double)c;
+                const double moved = 2.0 * (double)(x0v.v[i] - xv.v[i] * (T(1) + r.v[i])) / den;
+                const double d = (c >= T(0) && den > 0.0) ? moved : ((double)xn.v[i] - (double)xv.v[i]) * inv_tau;
+                acc += d * d;
+            }
+        }
+        if (STORE) {
+            vstore_s<T, V>(x + off, xn);
+            vstore_s<T, V>(x_bar + off, xb);
+        }
+        return acc;
+    }
+};
+template <typename T, int V> using CpPrimalKL = CpPrimalKLT<T, V, true>;
+template <typename T, int V> using CpPrimalKLRes = CpPrimalKLT<T, V, false>;
+
 // =============================================================================================
 // duality gap of 1/2 |x - x0|^2 + lambda |D x|_{2,1} at (x, qs = qscale q), reduce-only (tv_dual_gap): with gd = D^T qs
 //   gap = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda |D x|_2 - <qs, D x> ]      both parts >= 0 site by site for |qs|_2 <= lambda

@@ -7,10 +7,10 @@ Its iteration (Chambolle 2004) differs from Chambolle-Pock 2011, so iterates dif
 """
 import torch
 
-from .solvers import AcceleratedChambollePock, ChambollePock, RobustChambollePock
+from .solvers import AcceleratedChambollePock, ChambollePock, PoissonChambollePock, RobustChambollePock
 from .tv_operators_GPU import _to_device
 
-__all__ = ["denoise_tv_chambolle", "denoise_tv_robust"]
+__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson"]
 
 
 def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
@@ -75,6 +75,31 @@ def denoise_tv_robust(image, weight=1.0, fidelity="l1", delta=None, rel_res=1e-2
     else:
         raise ValueError("denoise_tv_robust: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
     cp = RobustChambollePock(vol.contiguous(), float(weight), fidelity=fidelity, delta=delta, scheme=scheme, reg_z_over_reg=1.0, tau=tau)
+    cp.run_until(rel_res, max_num_iter, check_every)
+    out = cp.result().reshape(x.shape)
+    return out if was_torch else out.detach().cpu().numpy()
+
+
+def denoise_tv_poisson(image, weight=1.0, rel_res=1e-2, max_num_iter=400, *, scheme="upwind", tau=None, check_every=10):
+    """Total-variation denoising of a 2-D (rows, cols) or 3-D (planes, rows, cols) image of photon COUNTS (Poisson noise: the variance of a
+    pixel equals its mean, so dark regions are cleaner than bright ones and a quadratic data term weighs them wrongly): minimises
+    KL(f, u) + weight * TV(u) over u >= 0 with the generalised Kullback-Leibler divergence KL(f, u) = sum (u - f + f log(f / u)).
+
+    image   : the counts, finite and >= 0 (ValueError otherwise); not rescaled -- the model depends on the absolute count level.
+    weight  : denoising weight (larger = smoother).
+    rel_res : stop when the optimality residual has dropped to rel_res times that of the start (``PoissonChambollePock.run_until``), checked
+              every ``check_every`` iterations, or after ``max_num_iter`` iterations.
+    tau     : the primal step; None = the balanced default of ``PoissonChambollePock``.
+    Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point, >= 0."""
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    if x.dim() == 2:
+        vol = x.reshape(1, 1, *x.shape)
+    elif x.dim() == 3:
+        vol = x.reshape(x.shape[0], 1, x.shape[1], x.shape[2])
+    else:
+        raise ValueError("denoise_tv_poisson: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
+    cp = PoissonChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0, tau=tau)
     cp.run_until(rel_res, max_num_iter, check_every)
     out = cp.result().reshape(x.shape)
     return out if was_torch else out.detach().cpu().numpy()

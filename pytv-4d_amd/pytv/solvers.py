@@ -13,6 +13,8 @@ fused HIP kernels (include/pytv4d.h):
                         with the step schedule of Chambolle & Pock 2011, Algorithm 2: O(1/k^2) instead of O(1/k)
     RobustChambollePock tv_cp_dual on the extrapolated point + tv_cp_primal_prox (D^T, pointwise prox of an L1 / Huber / L2 fidelity,
                         extrapolation)  (Nd+4): TV-L1 and TV-Huber for impulse noise (Chambolle & Pock 2011, section 6.2.2)
+    PoissonChambollePock tv_cp_dual on the extrapolated point + tv_cp_primal_kl (D^T, cancellation-free prox of the Kullback-Leibler
+                        fidelity, extrapolation)  (Nd+4): TV-KL for photon-counting data
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
     ADMM                tv_admm_tu / tv_admm_zu, tv_DT_axpy, tv_normal_op2 (I + rho D^T D from x alone, two dot products) +
                         tv_cg_update (single-reduction CG; textbook tv_cg_step1/2 kept)
@@ -31,7 +33,7 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
            "accel_schedule", "auto_pitch", "operator_norm_sq"]
 
 
@@ -551,7 +553,8 @@ class _SlabProblem:
 
     def _run_until_residual(self, rel_res, max_iter, check_every):
         """``run`` in blocks of ``check_every`` until ``residuals()["total"]`` <= rel_res**2 * ``initial_residual()`` at a check or ``max_iter``
-        iterations are done (the solvers without a duality gap: ``ChambollePockOperator``, ``RobustChambollePock``)."""
+        iterations are done (the solvers without a duality gap: ``ChambollePockOperator``, ``RobustChambollePock``,
+        ``PoissonChambollePock``)."""
         import numpy as np
         rel_res, max_iter, check_every = float(rel_res), int(max_iter), int(check_every)
         if check_every < 1 or max_iter < 0:
@@ -1130,7 +1133,8 @@ class ChambollePock(_SlabProblem):
 
 # =================================================================================================
 class _ExtrapolatedCP(_SlabProblem):
-    """What the Chambolle-Pock solvers with the state (x, x_bar, q) share (``AcceleratedChambollePock``, ``RobustChambollePock``): the state
+    """What the Chambolle-Pock solvers with the state (x, x_bar, q) share (``AcceleratedChambollePock``, ``RobustChambollePock``,
+    ``PoissonChambollePock``): the state
     and its halo planes, the dual half of an iteration -- tv_cp_dual on the extrapolated point x_bar -- and the loop around ``step``.  A
     subclass validates its steps (``cp_step_pair`` on ``L2``), calls ``_alloc_state`` and supplies ``step``: ``_dual_half`` + its primal
     kernel.  Per-step scalars: the slots of ``ChambollePock``."""
@@ -1315,7 +1319,46 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
 
 
 # =================================================================================================
-class RobustChambollePock(_ExtrapolatedCP):
+class _FixedPointResiduals:
+    """The optimality residual of the solvers whose fidelity has a pointwise prox but no cheap duality gap (``RobustChambollePock``,
+    ``PoissonChambollePock``): tv_cp_dual_residual for the dual block, the class's primal kernel in residual mode for the fidelity block.
+    The class supplies ``_prox(q, qp, qn, x, x_bar, theta, flags, out_ptr)`` (its primal entry point) and ``_fidelity_value()``, calls
+    ``_init_residuals`` at the end of its constructor, and keeps ``residuals`` / ``run_until`` with docstrings of its own."""
+
+    def _init_residuals(self):
+        """halo buffers of ``residuals`` (its own: the loop's are not touched), and R_0 of the starting pair, enqueued here and read back
+        (one synchronisation) only when somebody asks"""
+        self._res_buf = self._halo_set()
+        self._res0 = self._residual_scalars()
+        self._R0 = None
+
+    def _residual_scalars(self):
+        """fp64 device words [|D x|_{2,1}, R_q, R_x, fidelity] of the current pair on this rank; kernels and reductions are enqueued,
+        nothing waits for them.  Touches ``_res_buf`` and the workspace, never x, x_bar, q or the loop's halo planes."""
+        out = torch.zeros(4, dtype=torch.float64, device=self.device)
+        s, pl, b = self.slab, self.plan, self._res_buf
+        s.wait(pl.exchange_image(self.x, b["xp"], b["xn"]))
+        _nv.check(self.lib.tv_cp_dual_residual(self.geo.ref, _nv.ptr(self.x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(self.q), self.sigma,
+                                               self.reg, out[0:2].data_ptr(), _nv.ptr(self.ws), self.stream))
+        s.wait(pl.exchange_grad(self.q, _plane0(b["qp"]), _plane0(b["qn"])))
+        self._prox(self.q, b["qp"], b["qn"], self.x, None, 0.0, _nv.TV_CPP_RESIDUAL, out[2:3].data_ptr())
+        out[3] = self._fidelity_value()
+        return out
+
+    def _residual_dict(self, out):
+        self.slab.allreduce_sum_(out)                    # the four scalars in one call
+        tv, rq, rx, fid = (float(v) for v in out.cpu().tolist())
+        return {"x": rx, "q": rq, "total": rx + rq, "tv": tv, "fid": fid}
+
+    def initial_residual(self):
+        """R_0: ``residuals()["total"]`` of the pair the constructor left (x0, q = 0; enqueued there, read back on the first call)."""
+        if self._R0 is None:
+            self._R0 = self._residual_dict(self._res0)
+        return self._R0["total"]
+
+
+# =================================================================================================
+class RobustChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
     """min_x F(x - x0) + regularization * TV(x) for a ROBUST data term F (Chambolle & Pock 2011, section 6.2.2: TV-L1), with Algorithm 1
     of that paper (theta = 1, fixed steps).  ``fidelity``:
 
@@ -1342,8 +1385,8 @@ class RobustChambollePock(_ExtrapolatedCP):
     fixed-point (KKT) residual of the saddle problem, ``run_until`` stops on it.
 
     Not built (out of scope here): a one-sweep / fix-up form of the iteration, hipGraph capture, a persistent small-volume form, the placement
-    tuner / arena of ``ChambollePock``, and a Poisson / Kullback-Leibler fidelity (its prox is pointwise too, but needs a square root and
-    positivity handling of its own).
+    tuner / arena of ``ChambollePock``.  The Poisson / Kullback-Leibler fidelity (a pointwise prox with a square root and positivity
+    handling of its own) is ``PoissonChambollePock``.
 
     Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, F(x_new - x0) in slot ``F``."""
 
@@ -1361,11 +1404,7 @@ class RobustChambollePock(_ExtrapolatedCP):
         self.delta = float(delta) if fidelity == "huber" else 0.0
         self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
         self._alloc_state()
-        # halo buffers of ``residuals`` (its own: the loop's are not touched), and R_0 of the starting pair, enqueued here and read back
-        # (one synchronisation) only when somebody asks
-        self._res_buf = self._halo_set()
-        self._res0 = self._residual_scalars()
-        self._R0 = None
+        self._init_residuals()
 
     def _prox(self, q, qp, qn, x, x_bar, theta, flags, out_ptr):
         _nv.check(self.lib.tv_cp_primal_prox(self.geo.ref, _nv.ptr(q), _nv.ptr(qp), _nv.ptr(qn), _nv.ptr(x), _nv.ptr(x_bar), _nv.ptr(self.x0),
@@ -1406,24 +1445,6 @@ class RobustChambollePock(_ExtrapolatedCP):
         a = e.clamp(max=self.delta)
         return (e - a).sum(dtype=torch.float64) + torch.linalg.vector_norm(a, dtype=torch.float64) ** 2 / (2.0 * self.delta)
 
-    def _residual_scalars(self):
-        """fp64 device words [|D x|_{2,1}, R_q, R_x, F(x - x0)] of the current pair on this rank; kernels and reductions are enqueued,
-        nothing waits for them.  Touches ``_res_buf`` and the workspace, never x, x_bar, q or the loop's halo planes."""
-        out = torch.zeros(4, dtype=torch.float64, device=self.device)
-        s, pl, b = self.slab, self.plan, self._res_buf
-        s.wait(pl.exchange_image(self.x, b["xp"], b["xn"]))
-        _nv.check(self.lib.tv_cp_dual_residual(self.geo.ref, _nv.ptr(self.x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(self.q), self.sigma,
-                                               self.reg, out[0:2].data_ptr(), _nv.ptr(self.ws), self.stream))
-        s.wait(pl.exchange_grad(self.q, _plane0(b["qp"]), _plane0(b["qn"])))
-        self._prox(self.q, b["qp"], b["qn"], self.x, None, 0.0, _nv.TV_CPP_RESIDUAL, out[2:3].data_ptr())
-        out[3] = self._fidelity_value()
-        return out
-
-    def _residual_dict(self, out):
-        self.slab.allreduce_sum_(out)                    # the four scalars in one call
-        tv, rq, rx, fid = (float(v) for v in out.cpu().tolist())
-        return {"x": rx, "q": rq, "total": rx + rq, "tv": tv, "fid": fid}
-
     def residuals(self):
         """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": F(x - x0)} of the current pair (x, q) as Python floats, between
         ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the scalars, one host
@@ -1432,11 +1453,108 @@ class RobustChambollePock(_ExtrapolatedCP):
         return self._residual_dict(self._residual_scalars())
     residuals.__doc__ += _RES_DOC
 
-    def initial_residual(self):
-        """R_0: ``residuals()["total"]`` of the pair the constructor left (x0, q = 0; enqueued there, read back on the first call)."""
-        if self._R0 is None:
-            self._R0 = self._residual_dict(self._res0)
-        return self._R0["total"]
+    def run_until(self, rel_res, max_iter, check_every=10):
+        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
+        first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the pair the constructor left
+        (x0, q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
+        Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
+        ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 2-word pass and the fidelity reduction.
+        """
+        return self._run_until_residual(rel_res, max_iter, check_every)
+    run_until.__doc__ += _RES_DOC
+
+
+# =================================================================================================
+class PoissonChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
+    """min_{x >= 0} F(x) + regularization * TV(x) for POISSON (photon-counting) data x0 >= 0 -- CT projections, low-dose frames,
+    fluorescence stacks --, where the maximum-likelihood data term is the generalised Kullback-Leibler divergence
+
+        F(x) = sum_i ( x_i - x0_i + x0_i log(x0_i / x_i) )        >= 0, zero at x = x0; 0 log 0 = 0; +inf where x_i = 0 < x0_i
+
+    with Algorithm 1 of Chambolle & Pock 2011 (theta = 1, fixed steps; F is not strongly convex on x >= 0, so there is no accelerated
+    schedule).  State: x, x_bar (images), q (gradient); x = x_bar = x0, q = 0 at the start.  One iteration:
+
+        q     <- proj_{|.|_2 <= reg}(q + sigma D x_bar)                             tv_cp_dual on x_bar        (2 Nd + 1 words per voxel)
+        v      = x - tau D^T q;  b = v - tau
+        x_new <- prox_{tau F}(v) = (b + sqrt(b^2 + 4 tau x0)) / 2
+        x_bar <- 2 x_new - x;  x <- x_new                                           tv_cp_primal_kl, one pass  (Nd + 4)
+
+    -- 3 Nd + 5 words per voxel, the loop of ``RobustChambollePock`` with another pointwise prox.  The kernel takes the root in a form
+    without cancellation (2 tau x0 / (sqrt(..) - b) where b < 0), so the iterate is >= 0 everywhere, a site with x0 = 0 goes to exactly 0
+    once b < 0, and the loss stays finite.  Sharded (``slab``): as ``RobustChambollePock``.
+
+    STEPS.  tau sigma L^2 <= 1 with L^2 = ``normal_spectral_bound``; both default to 1 / sqrt(L^2), one given: the other is 1 / (L^2 times
+    it).  ``residuals()`` gives the fixed-point (KKT) residual of the saddle problem, ``run_until`` stops on it.  (A duality gap would need
+    1 + D^T q > 0 at every site, which the iterates do not guarantee.)
+
+    Not built: a one-sweep / fix-up form of the iteration, hipGraph capture, a persistent small-volume form, the placement tuner / arena
+    of ``ChambollePock``, and a background term.
+
+    Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, F(x_new) in slot ``F``."""
+
+    def __init__(self, x0, regularization, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
+                 factor_reg_static=0, tau=None, sigma=None, slab=None, pitch="auto"):
+        """x0: the counts, >= 0 and finite (ValueError otherwise: one min / max reduction; sharded: collective, every rank raises).  tau,
+        sigma: see the class docstring -- tau * sigma * L^2 > 1 + 1e-12 raises ValueError.  pitch: see ``_SlabProblem``."""
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
+        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        lo, hi = torch.aminmax(x0)                       # NaN propagates through both
+        bad = (~((lo >= 0) & torch.isfinite(hi))).to(torch.float64).reshape(1)
+        self.slab.allreduce_sum_(bad)
+        if float(bad.item()) != 0.0:
+            raise ValueError("PoissonChambollePock: x0 must be counts -- finite and >= 0 everywhere")
+        self._alloc_state()
+        self._init_residuals()
+
+    def _prox(self, q, qp, qn, x, x_bar, theta, flags, out_ptr):
+        _nv.check(self.lib.tv_cp_primal_kl(self.geo.ref, _nv.ptr(q), _nv.ptr(qp), _nv.ptr(qn), _nv.ptr(x), _nv.ptr(x_bar), _nv.ptr(self.x0),
+                                           self.tau, theta, flags, out_ptr, _nv.ptr(self.ws), self.stream))
+
+    def step(self, out=None):
+        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
+        F(x_new) in slot F; defaults to an internal scratch."""
+        out = self._scratch if out is None else out
+        self._dual_half(self.sigma, out)
+        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[self.F:self.F + 1].data_ptr())
+        self.it += 1
+
+    def run(self, n_iter, record_loss=True):
+        """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
+        None.  Row k is F(x_{k+1}) + reg |D x_bar_k|_{2,1}: the TV term is that of the extrapolated point the dual step saw -- a progress
+        indicator in the slots of ``ChambollePock``'s history; the objective of the current iterate is
+        ``residuals()["fid"] + reg * residuals()["tv"]``."""
+        return self._run(n_iter, record_loss)
+
+    _RES_DOC = """(x, q) is a saddle point of  min_{x >= 0} max_{|q|_2 <= reg}  F(x) + <D x, q>  (whose x solves the problem) iff it is a fixed point
+        of both updates of the iteration.  The residual R = R_x + R_q:
+            R_x = |x - prox_{tau F}(x - tau D^T q)|^2 / tau^2                zero iff -D^T q is in the subdifferential of F at x:
+                                                                             tv_cp_primal_kl in residual mode, Nd + 2 words per voxel
+            R_q = |q - proj(q + sigma D x)|^2 / sigma^2                      zero iff q is in the subdifferential of reg |.|_2 at D x:
+                                                                             tv_cp_dual_residual, Nd + 1 words per voxel
+        both summed site by site in fp64 by reduce-only kernels.  fp32: R_x is resolved down to about (eps_fp32 |x| / tau)^2 per voxel."""
+
+    _FID_CHUNK = 1 << 24          # elements per fp64 temporary of ``_fidelity_value``
+
+    def _fidelity_value(self):
+        """F(x) of this rank as a 0-d fp64 device tensor: torch arithmetic in fp64 (0 log 0 = 0; +inf where x = 0 < x0), a few planes at
+        a time so that the fp64 temporaries stay small.  Called once per check, never inside the loop (the loop's own fidelity scalar
+        comes out of tv_cp_primal_kl)."""
+        nz = self.x.shape[0]
+        planes = max(1, self._FID_CHUNK // max(1, self.x[0].numel()))
+        total = torch.zeros((), dtype=torch.float64, device=self.device)
+        for a in range(0, nz, planes):
+            x, c = self.x[a:a + planes].double(), self.x0[a:a + planes].double()
+            ratio = torch.where(c > 0, c / x, torch.ones_like(c))
+            total += (x - c).sum() + torch.xlogy(c, ratio).sum()
+        return total
+
+    def residuals(self):
+        """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": F(x)} of the current pair (x, q) as Python floats, between
+        ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the scalars, one host
+        synchronisation.  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._residual_dict(self._residual_scalars())
+    residuals.__doc__ += _RES_DOC
 
     def run_until(self, rel_res, max_iter, check_every=10):
         """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the

@@ -276,6 +276,39 @@ int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void*
 int tv_cp_dual_residual(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, double sigma_D,
                         double lambda, double* out, void* ws, void* stream);
 
+/* Dual step of Chambolle-Pock for the HUBER-TV regulariser (Chambolle & Pock 2011, section 6.2.1: the Huber-ROF model against staircasing)
+ *   P(x) = 1/2 |x - x0|^2 + lambda sum_sites h_alpha(|D x|_2),   h_alpha(t) = t^2 / (2 alpha) for t <= alpha, t - alpha / 2 beyond:
+ * quadratic below a gradient magnitude alpha, TV above it.  The conjugate of the regulariser gains (alpha / 2 lambda) |q|^2, so
+ *   v = (q + sigma_D D x) / (1 + sigma_D alpha / lambda);   q <- v / max(1, |v|_2 / lambda)      (shrink, then project)
+ *   *hub (device fp64) = sum_sites h_alpha(|D x|_2) of the local planes, each site as (n - a) + a^2 / (2 alpha), a = min(n, alpha), in fp64.
+ * 1 / (1 + sigma_D alpha / lambda) is formed once in double.  The primal half of the iteration is tv_cp_primal_accel with constant tau and
+ * theta (Algorithm 3 of the paper: both halves of the saddle problem are strongly convex; pytv.solvers.cp_linear_steps).
+ * 2 Nd + 1 words per voxel; q is written in place, nothing else but hub and ws.  x_prev / x_next, alignment and dispatch as tv_cp_dual: four
+ * schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays -- pads stay zero --, mask_static / time_factor / time_weight_vol,
+ * z-slabs; fp32 planes of >= 4 MiB take the plane-marching kernel (not central / hybrid with 16 frames: those instantiations would spill to
+ * scratch and do not exist; the one-site kernel runs there).
+ * TV_E_ARG: a NULL array, lambda, alpha or sigma_D not finite and > 0 (alpha = 0 is tv_cp_dual's model and is refused), a tv_geom of
+ * another interface version; a missing halo plane is TV_E_HALO as in tv_cp_dual; all checks precede any device access. */
+int tv_cp_dual_huber(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q,
+                     double sigma_D, double lambda, double alpha, double* hubout, void* ws, void* stream);
+
+/* Duality-gap certificate of the Huber-TV model above for an iterate x and a dual variable q with |q|_2 <= lambda per site (what
+ * tv_cp_dual_huber leaves).  Dual(q) = <gd, x0> - 1/2 |gd|^2 - (alpha / 2 lambda) |q|^2 with gd = D^T q.  Over the local planes
+ *   out[0] = sum_sites h_alpha(|D x|_2)
+ *   out[1] = 1/2 |x - x0|^2
+ *   out[2] = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda h_alpha(|D x|_2) - <q, D x> + (alpha / 2 lambda) |q|^2 ]  =  P(x) - Dual(q)
+ * Both parts of a site's term are >= 0 (Fenchel-Young).  Where |D x|_2 <= alpha the second part is summed as the perfect square
+ * (lambda / 2 alpha) |D x - (alpha / lambda) q|^2, exactly >= 0; beyond alpha as lambda (|D x|_2 - alpha / 2) - <q, D x> + (alpha / 2 lambda) |q|^2.
+ * Accumulated in fp64 from the stencil results of the array dtype, never as P - Dual, not clamped.  The caller has
+ * P = out[1] + lambda * out[0], Dual = P - out[2], and 1/2 |x - x*|^2 <= out[2].
+ * REDUCE-ONLY: nothing is written except out (three device fp64 words) and ws.  x_prev / x_next as in tv_cp_dual, q_prev / q_next as in
+ * tv_DT; slab partials add up to the unsharded scalars.  Every geometry of tv_dual_gap: one launch of the one-site-per-thread kernel,
+ * Nd + 2 words per voxel, large planes too (the call is made once per convergence check; there is no plane-marching form).
+ * TV_E_ARG: a NULL array, lambda or alpha not finite and > 0, a tv_geom of another interface version; a missing halo plane is
+ * TV_E_HALO; all checks precede any device access. */
+int tv_dual_gap_huber(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                      const void* q_next, const void* x0, double lambda, double alpha, double* out, void* ws, void* stream);
+
 /* One-sweep form of the same iteration (all four schemes; fp32, nx % 4 == 0, nx >= 64,
  * any m: more than 8 frames are processed as time windows of 8): q is read and written ONCE per
  * iteration.  x is ping-ponged.

@@ -324,6 +324,12 @@ namespace tvm {
 int D_store(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb, float* dout);
 int D_cp_dual(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
               float* q, float sigma, float inv_lambda, double* partials);
+// the same for the Huber-TV regulariser (tv_cp_dual_huber; CpDualHuber of tv_stencil.h): sum h_alpha(|D x|_2) instead of |D x|_{2,1}.
+// Not (central / hybrid, M = 16): those instantiations would use scratch and are left out -- D_cp_dual_huber_ok answers false, the
+// one-site kernel does the work
+bool D_cp_dual_huber_ok(const tv_geom* g, const DG& d);
+int D_cp_dual_huber(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
+                    float* q, float sigma, float shrink, float inv_lambda, double alpha, double half_inv_alpha, double* partials);
 // sub-gradient passes on the marching path: pass 1 = |Dx| (0 -> +inf) on the local planes plus ghost planes,
 // pass 2 = G from x and |Dx| (radius-1 schemes only); x halo buffers hold TWO planes each
 int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,

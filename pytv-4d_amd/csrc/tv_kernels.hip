@@ -6,12 +6,14 @@
 //                StoreD   -> materialise the gradient            (tv_D)
 //                NormEpi  -> 1/|Dx|_2 per voxel + TV partials    (tv_subgrad pass 1)
 //                CpDual   -> q <- proj(q + sigma D x)            (tv_cp_dual)
+//                CpDualHuber -> the same with the Huber-TV shrink (tv_cp_dual_huber)
 //                AdmmZU   -> z/u update of ADMM                  (tv_admm_zu)
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
 //                StoreDT / AxpyDT / CpPrimal / CpPrimalAccel epilogues   (tv_DT, tv_DT_axpy, tv_cp_primal, tv_cp_primal_accel)
 //                CpPrimalProxT -> primal step with an L2 / L1 / Huber prox, or its reduce-only residual   (tv_cp_primal_prox)
 //                CpPrimalKLT   -> primal step with the Poisson / Kullback-Leibler prox, or its residual     (tv_cp_primal_kl)
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
+//   k_gap_huber : the same for the Huber-TV regulariser  (tv_dual_gap_huber)
 //   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
 //   k_normal_vec  / k_normal_central_vec  : x + rho D^T D x from x alone   (tv_normal_op)
@@ -93,6 +95,44 @@ __global__ __launch_bounds__(256) void k_gap(DG g, WT<T> w, const T* x, const T*
     const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
     const double tv = block_sum(a[0], sm);
     if (first) p_tv[b] = tv;
+    const double fid = block_sum(a[1], sm);
+    if (first) p_fid[b] = fid;
+    const double gap = block_sum(a[2], sm);
+    if (first) p_gap[b] = gap;
+}
+
+// the Huber-TV form of the above (tv_dual_gap_huber): the same two stencils at one site, the three sums of gap_terms_huber (tv_stencil.h)
+template <int S, typename T, int V> struct GapSiteHuber {
+    static constexpr bool REDUCES = true;
+    WT<T> w;
+    SrcScaled<T, V> src;     // (scale 1: the gather through SrcPlain's loads costs 32 bytes of scratch per lane, k_DT's known pattern)
+    const T* x;
+    const T* x0;
+    HuberGapConsts k;
+    double* acc3;        // the calling thread's three sums
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        long long inpl;
+        const Vec<T, V> gd = dt_site<S, T, V>(g, w, src, c, inpl);
+        const long long offd = (long long)c.zl * g.s_dz + inpl, off = (long long)c.zl * g.s_z + inpl;
+        Vec<T, V> qv[8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) qv[s] = vsplat<T, V>(T(0));
+        for_each_channel<S>(g, [&](auto slot, int ch) { qv[decltype(slot)::value] = src.ld(offd + (long long)ch * g.s_z); });
+        gap_terms_huber<T, V>(o, qv, vload<T, V>(x + off), vload<T, V>(x0 + off), gd, k, acc3[0], acc3[1], acc3[2]);
+        return 0.0;
+    }
+};
+template <int S, typename T, int V>
+__global__ __launch_bounds__(256) void k_gap_huber(DG g, WT<T> w, const T* x, const T* xp, const T* xn, SrcScaled<T, V> src, const T* x0,
+                                                    HuberGapConsts k, double* p_hub, double* p_fid, double* p_gap) {
+    __shared__ double sm[16];
+    const Coord c = thread_coord<V>(g, 0);
+    double a[3] = {0.0, 0.0, 0.0};
+    d_site<S, T, V>(g, w, x, xp, xn, 1, c, GapSiteHuber<S, T, V>{w, src, x, x0, k, a}, PlainMem());
+    const long long b = linear_block_id();
+    const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
+    const double hub = block_sum(a[0], sm);
+    if (first) p_hub[b] = hub;
     const double fid = block_sum(a[1], sm);
     if (first) p_fid[b] = fid;
     const double gap = block_sum(a[2], sm);
@@ -959,6 +999,38 @@ int tv_cp_dual(const tv_geom* g, const void* x, const void* x_prev, const void* 
     });
 }
 
+// Dual step for the Huber-TV regulariser (include/pytv4d.h): tv_cp_dual's halo, alignment and launch rules with the CpDualHuber epilogue.
+// shrink = 1 / (1 + sigma alpha / lambda) and 1 / (2 alpha) are formed here in double; every argument check precedes the first device access.
+static inline bool finite_pos(double v) { return std::isfinite(v) && v > 0.0; }
+int tv_cp_dual_huber(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q, double sigma_D,
+                     double lambda, double alpha, double* hubout, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (x == nullptr || q == nullptr || hubout == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
+    if (!finite_pos(lambda)) return fail(TV_E_ARG, "lambda must be a finite number > 0");
+    if (!finite_pos(alpha)) return fail(TV_E_ARG, "alpha must be a finite number > 0 (alpha = 0 is plain TV: tv_cp_dual)");
+    if (!finite_pos(sigma_D)) return fail(TV_E_ARG, "sigma_D must be a finite number > 0");
+    if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
+    const double shrink = 1.0 / (1.0 + sigma_D * alpha / lambda), inv_lambda = 1.0 / lambda, half_inv_alpha = 0.5 / alpha;
+    if (march_ok(g, d, vec) && tvm::D_cp_dual_huber_ok(g, d)) {
+        long long nb;
+        if (int rc = tvm::D_cp_dual_huber(g, d, x, x_prev, x_next, st, &nb, (float*)q, (float)sigma_D, (float)shrink, (float)inv_lambda, alpha,
+                                          half_inv_alpha, P.slot(0))) return rc;
+        return P.reduce(0, nb, hubout, st);
+    }
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        CpDualHuber<S, T, V> epi{(T*)q, (T)sigma_D, (T)shrink, (T)inv_lambda, alpha, half_inv_alpha, P.slot(0)};
+        hipLaunchKernelGGL((k_D<S, T, V, CpDualHuber<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
+                           (const T*)x_prev, (const T*)x_next, 1, 0, epi);
+        HIP_TRY(hipGetLastError());
+        return P.reduce(0, lc.nblocks, hubout, st);
+    });
+}
+
 int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, const void* x0,
                  void* p, double tau, double sigma_A, double* fid, void* ws, void* stream) {
     DG d;
@@ -1138,6 +1210,33 @@ int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void*
                            src, (const T*)x0, lambda, P.slot(0), P.slot(1), P.slot(2));
         HIP_TRY(hipGetLastError());
         return reduce3(lc.nblocks);
+    });
+}
+
+// P(x) - Dual(q) of the Huber-TV model, with its two by-products; reduce-only (include/pytv4d.h).  Always the one-site kernel, large planes
+// too: like tv_cp_dual_residual this runs once per convergence check.  Every argument check precedes the first device access.
+int tv_dual_gap_huber(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                      const void* q_next, const void* x0, double lambda, double alpha, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (x == nullptr || q == nullptr || x0 == nullptr || out == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
+    if (!finite_pos(lambda)) return fail(TV_E_ARG, "lambda must be a finite number > 0");
+    if (!finite_pos(alpha)) return fail(TV_E_ARG, "alpha must be a finite number > 0 (alpha = 0 is plain TV: tv_dual_gap)");
+    if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
+    if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, q_prev, q_next, x0, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);                              // slot 0: sum h_alpha(|D x|_2), slot 1: 1/2 |x - x0|^2, slot 2: the gap
+    const HuberGapConsts k{lambda, alpha, 0.5 / alpha, alpha / lambda, 0.5 * lambda / alpha, 0.5 * alpha / lambda};
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        SrcScaled<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next, T(1)};
+        hipLaunchKernelGGL((k_gap_huber<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
+                           src, (const T*)x0, k, P.slot(0), P.slot(1), P.slot(2));
+        HIP_TRY(hipGetLastError());
+        for (int s = 0; s < 3; ++s)
+            if (int rc = P.reduce(s, lc.nblocks, out + s, st)) return rc;
+        return 0;
     });
 }
 

@@ -3,18 +3,24 @@
 #include "tv_stencil.h"
 #include "tv_march.h"
 
-template <template <int, typename, int> class EpiT, typename... Args>
+// NO_WIDE16: leave out M = 16 of the schemes with a 16-frame-wide working set (central, hybrid), where an 8-vector epilogue spills
+// (CpDual: 164 / 340 bytes of scratch per lane); the caller keeps those geometries on the one-site kernel (tvm::D_cp_dual_huber_ok)
+template <template <int, typename, int> class EpiT, bool NO_WIDE16 = false, typename... Args>
 static int launch_D_march(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st,
                           long long* nblocks, Args... args) {
     const int zc = march_zchunk(d);
     const LC lc = march_cfg(d, zc);
     *nblocks = lc.nblocks;
     return dispatch_scheme_m(MarchMs{}, g->scheme, d.m, kNoMarchSM, [&]<int S, int M>() -> int {
-        EpiT<S, float, 4> epi{args...};
-        hipLaunchKernelGGL((k_D_march<S, M, EpiT<S, float, 4>>), lc.grid, lc.block, 0, st, d, make_w<float>(g), (const float*)x,
-                           (const float*)xp, (const float*)xn, zc, epi);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        if constexpr (NO_WIDE16 && M == 16 && (S == CENTRAL || S == HYBRID)) {
+            return fail(TV_E_ARG, kNoMarchSM);
+        } else {
+            EpiT<S, float, 4> epi{args...};
+            hipLaunchKernelGGL((k_D_march<S, M, EpiT<S, float, 4>>), lc.grid, lc.block, 0, st, d, make_w<float>(g), (const float*)x,
+                               (const float*)xp, (const float*)xn, zc, epi);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
     });
 }
 
@@ -26,6 +32,11 @@ int D_cp_dual(const tv_geom* g, const DG& d, const void* x, const void* xp, cons
               float* q, float sigma, float inv_lambda, double* partials) {
     return launch_D_march<CpDual>(g, d, x, xp, xn, st, nb, q, sigma, inv_lambda, partials);
 }
+int D_cp_dual_huber(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
+                    float* q, float sigma, float shrink, float inv_lambda, double alpha, double half_inv_alpha, double* partials) {
+    return launch_D_march<CpDualHuber, true>(g, d, x, xp, xn, st, nb, q, sigma, shrink, inv_lambda, alpha, half_inv_alpha, partials);
+}
+bool D_cp_dual_huber_ok(const tv_geom* g, const DG& d) { return !(d.m == 16 && (g->scheme == TV_CENTRAL || g->scheme == TV_HYBRID)); }
 int D_admm_zu(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
               float* z, float* u, float thresh, double* partials, int tform) {
     return launch_D_march<AdmmZU>(g, d, x, xp, xn, st, nb, z, u, thresh, partials, tform);

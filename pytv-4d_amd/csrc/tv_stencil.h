@@ -272,6 +272,51 @@ template <int S, typename T, int V> struct CpDual {
     }
 };
 
+// Chambolle-Pock dual update for the HUBER-TV regulariser lambda sum h_alpha(|D x|_2), h_alpha(t) = t^2 / (2 alpha) for t <= alpha and
+// t - alpha / 2 beyond (Chambolle & Pock 2011, section 6.2.1): the conjugate gains (alpha / 2 lambda) |q|^2, so its prox shrinks before it
+// projects.  The arithmetic of one site: v = (q + sigma D x) * shrink per channel with shrink = 1 / (1 + sigma alpha / lambda) (formed in
+// double by the host), scale = 1 / max(1, |v|_2 / lambda) per column -- the new q is v * scale; returns sum over the columns of
+// h_alpha(n), n = |D x|_2, as (n - a) + a^2 / (2 alpha) with a = min(n, alpha): no branch, fp64.  cp_dual_site's sibling: ONE body for the
+// update (CpDualHuber), whatever kernel form calls it.
+template <int S, typename T, int V>
+__device__ __forceinline__ double cp_dual_huber_site(const DG& g, const T* base, const Vec<T, V> (&o)[8], T sigma, T shrink, T inv_lambda,
+                                                     double alpha, double half_inv_alpha, Vec<T, V> (&v)[8], Vec<T, V>& scale) {
+    Vec<T, V> vs = vsplat<T, V>(T(0));
+    for_each_channel<S>(g, [&](auto slot, int ch) {
+        constexpr int k = decltype(slot)::value;
+        v[k] = shrink * (vload_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z) + sigma * o[k]);
+        vs = vs + v[k] * v[k];
+    });
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const double n = (double)tsqrt(ds.v[i]);
+        const double a = fmin(n, alpha);
+        acc += (n - a) + (a * a) * half_inv_alpha;
+        scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * inv_lambda);
+    }
+    return acc;
+}
+template <int S, typename T, int V> struct CpDualHuber {
+    static constexpr bool REDUCES = true;
+    T* q;
+    T sigma, shrink, inv_lambda;
+    double alpha, half_inv_alpha;
+    double* partials;
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        T* base = q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        Vec<T, V> v[8];
+        Vec<T, V> scale;
+        const double acc = cp_dual_huber_site<S, T, V>(g, base, o, sigma, shrink, inv_lambda, alpha, half_inv_alpha, v, scale);
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            constexpr int k = decltype(slot)::value;
+            vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);
+        });
+        return acc;
+    }
+};
+
 // ADMM: v = Dx + u;  z = v * max(0, 1 - thresh/|v|);  u = v - z.   tform: the first array receives t = z - u_new
 // (= 2 z - v) instead of z: the next right-hand side x0 + rho D^T (z - u) then reads ONE gradient array
 template <int S, typename T, int V> struct AdmmZU {
@@ -645,6 +690,41 @@ __device__ __forceinline__ void gap_terms(const Vec<T, V> (&o)[8], const Vec<T, 
             a_gap += 0.5 * r * r;
         }
     }
+}
+// The same three terms for the Huber-TV model 1/2 |x - x0|^2 + lambda sum h_alpha(|D x|_2) at (x, q), |q|_2 <= lambda (tv_dual_gap_huber):
+//   gap = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda h_alpha(|D x|_2) - <q, D x> + (alpha / 2 lambda) |q|^2 ]
+// The regulariser part is >= 0 site by site (Fenchel-Young).  Where |D x|_2 <= alpha it IS the square (lambda / 2 alpha) |D x - (alpha /
+// lambda) q|^2 and is summed as that square; beyond alpha it is lambda (n - alpha / 2) - <q, D x> + (alpha / 2 lambda) |q|^2.  a_hub
+// receives h_alpha(|D x|_2) in cp_dual_huber_site's form.  The constants are host doubles; fp64 throughout, from the T-valued stencil results.
+struct HuberGapConsts {
+    double lambda, alpha, half_inv_alpha;      // 1 / (2 alpha)
+    double a_over_l, l_over_2a, a_over_2l;     // alpha / lambda, lambda / (2 alpha), alpha / (2 lambda)
+};
+template <typename T, int V>
+__device__ __forceinline__ void gap_terms_huber(const Vec<T, V> (&o)[8], const Vec<T, V> (&qv)[8], const Vec<T, V>& xv, const Vec<T, V>& x0v,
+                                                const Vec<T, V>& gd, const HuberGapConsts& k, double& a_hub, double& a_fid, double& a_gap) {
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    // one column at a time, its index a compile-time constant: the nested channel loop keeps the compiler from unrolling a run-time
+    // column loop, and a run-time index into the lanes puts them into scratch
+    auto column = [&]<int I>(IC<I>) {
+        const double n = (double)tsqrt(ds.v[I]);
+        const double a = fmin(n, k.alpha);
+        double sq = 0.0, dot = 0.0, qq = 0.0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {                                  // inactive slots are exactly zero in o and in qv
+            const double d = (double)o[c].v[I], qc = (double)qv[c].v[I];
+            const double e = d - k.a_over_l * qc;
+            sq += e * e;
+            dot += qc * d;
+            qq += qc * qc;
+        }
+        const double e = (double)xv.v[I] - (double)x0v.v[I];
+        const double r = e + (double)gd.v[I];
+        a_hub += (n - a) + (a * a) * k.half_inv_alpha;
+        a_fid += 0.5 * e * e;
+        a_gap += 0.5 * r * r + (n <= k.alpha ? k.l_over_2a * sq : k.lambda * (n - 0.5 * k.alpha) - dot + k.a_over_2l * qq);
+    };
+    [&]<int... I>(std::integer_sequence<int, I...>) { (column(IC<I>{}), ...); }(std::make_integer_sequence<int, V>{});
 }
 // D-side pass of the plane-marching form (k_D_march): |D x|_{2,1}, 1/2 |x - x0|^2 and sum (lambda |D x|_2 - <qs, D x>); reads x0 and q once.
 // The D^T-side pass (GapDT) ran BEFORE it on the same grid and left its per-block sums in `partials`: finish() adds to them.

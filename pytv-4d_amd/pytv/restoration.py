@@ -7,10 +7,10 @@ Its iteration (Chambolle 2004) differs from Chambolle-Pock 2011, so iterates dif
 """
 import torch
 
-from .solvers import AcceleratedChambollePock, ChambollePock, PoissonChambollePock, RobustChambollePock
+from .solvers import AcceleratedChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock, RobustChambollePock
 from .tv_operators_GPU import _to_device
 
-__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson"]
+__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber"]
 
 
 def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
@@ -101,5 +101,30 @@ def denoise_tv_poisson(image, weight=1.0, rel_res=1e-2, max_num_iter=400, *, sch
         raise ValueError("denoise_tv_poisson: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
     cp = PoissonChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0, tau=tau)
     cp.run_until(rel_res, max_num_iter, check_every)
+    out = cp.result().reshape(x.shape)
+    return out if was_torch else out.detach().cpu().numpy()
+
+
+def denoise_tv_huber(image, weight=0.1, alpha=1.0, rel_gap=1e-4, max_num_iter=200, *, scheme="upwind", check_every=10):
+    """Denoising of a 2-D (rows, cols) or 3-D (planes, rows, cols) image with the HUBER-TV regulariser, the standard remedy for the
+    staircasing of plain TV (smooth ramps coming back as terraces): minimises 1/2 |u - f|^2 + weight * sum h_alpha(|grad u|), where
+    h_alpha is quadratic below a gradient magnitude ``alpha`` and linear -- TV -- above it (Chambolle & Pock 2011, section 6.2.1).
+
+    weight : denoising weight (larger = smoother), as in ``denoise_tv_chambolle``.
+    alpha  : the gradient magnitude, in grey levels per pixel, below which the model smooths instead of preserving an edge; finite and > 0
+             (alpha -> 0 is ``denoise_tv_chambolle``).  It scales with the grey levels of the image.
+    rel_gap: stop when the duality gap certifies the answer, gap <= rel_gap * objective at a check (``HuberChambollePock.run_until``:
+             1/2 |u - u*|^2 <= gap), checked every ``check_every`` iterations, or after ``max_num_iter`` iterations.
+    Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point."""
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    if x.dim() == 2:
+        vol = x.reshape(1, 1, *x.shape)
+    elif x.dim() == 3:
+        vol = x.reshape(x.shape[0], 1, x.shape[1], x.shape[2])
+    else:
+        raise ValueError("denoise_tv_huber: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
+    cp = HuberChambollePock(vol.contiguous(), float(weight), float(alpha), scheme=scheme, reg_z_over_reg=1.0)
+    cp.run_until(rel_gap, max_num_iter, check_every)
     out = cp.result().reshape(x.shape)
     return out if was_torch else out.detach().cpu().numpy()

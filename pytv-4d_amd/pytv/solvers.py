@@ -15,6 +15,8 @@ fused HIP kernels (include/pytv4d.h):
                         extrapolation)  (Nd+4): TV-L1 and TV-Huber for impulse noise (Chambolle & Pock 2011, section 6.2.2)
     PoissonChambollePock tv_cp_dual on the extrapolated point + tv_cp_primal_kl (D^T, cancellation-free prox of the Kullback-Leibler
                         fidelity, extrapolation)  (Nd+4): TV-KL for photon-counting data
+    HuberChambollePock  tv_cp_dual_huber on the extrapolated point (shrink + projection, Huber partial) + tv_cp_primal_accel with fixed steps:
+                        the Huber-TV regulariser against staircasing, linearly convergent (Chambolle & Pock 2011, Algorithm 3)
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
     ADMM                tv_admm_tu / tv_admm_zu, tv_DT_axpy, tv_normal_op2 (I + rho D^T D from x alone, two dot products) +
                         tv_cg_update (single-reduction CG; textbook tv_cg_step1/2 kept)
@@ -33,8 +35,8 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
-           "accel_schedule", "auto_pitch", "operator_norm_sq"]
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "HuberChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+           "accel_schedule", "cp_linear_steps", "auto_pitch", "operator_norm_sq"]
 
 
 def cp_step_size(nz_global, m, reg_z_over_reg, reg_time, time_weight_max=1.0):
@@ -97,6 +99,21 @@ def accel_schedule(tau0, sigma0, gamma, n, start=0):
         t = th * t
     sigma = sigma0 * (tau0 / tau)
     return tau[start:].copy(), sigma[start:].copy(), theta[start:].copy()
+
+
+def cp_linear_steps(L2, gamma, delta):
+    """(tau, sigma, theta, mu) of the LINEARLY convergent Chambolle-Pock iteration (Chambolle & Pock 2011, Algorithm 3) for a saddle problem
+    whose primal term is gamma-strongly convex and whose dual term is delta-strongly convex, |K|^2 <= ``L2``, as Python floats:
+        mu = 2 sqrt(gamma delta) / sqrt(L2),  tau = mu / (2 gamma),  sigma = mu / (2 delta),  theta = 1 / (1 + mu)
+    so that tau sigma L2 = 1; the iterates converge as O(omega^k) with omega = (1 + theta) / (2 + mu) < 1.  sigma is formed as
+    1 / (L2 tau) -- the same number, and the product then equals 1 to three roundings whatever the arguments.  ValueError unless the
+    three arguments are finite and > 0."""
+    L2, gamma, delta = float(L2), float(gamma), float(delta)
+    if not all(math.isfinite(v) and v > 0.0 for v in (L2, gamma, delta)):
+        raise ValueError("cp_linear_steps: L2, gamma and delta must be finite and > 0")
+    mu = 2.0 * math.sqrt(gamma * delta) / math.sqrt(L2)
+    tau = mu / (2.0 * gamma)
+    return tau, 1.0 / (L2 * tau), 1.0 / (1.0 + mu), mu
 
 
 def operator_norm_sq(A, AT, like, n_iter=20, seed=0, slab=None):
@@ -524,12 +541,17 @@ class _SlabProblem:
         s.wait(pl.exchange_image(x, b["xp"], b["xn"]))
         s.wait(pl.exchange_grad(q, _plane0(b["qp"]), _plane0(b["qn"])))
         out = b["out"]
-        _nv.check(self.lib.tv_dual_gap(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]), _nv.ptr(b["qn"]),
-                                       _nv.ptr(self.x0), self.reg, float(qscale), out.data_ptr(), _nv.ptr(self.ws), self.stream))
+        self._gap_kernel(x, q, qscale, b, out)
         s.allreduce_sum_(out)
         tv, fid, gap = (float(v) for v in out.cpu().tolist())
         primal = fid + self.reg * tv
         return primal, primal - gap, gap
+
+    def _gap_kernel(self, x, q, qscale, b, out):
+        """the reduce-only entry point of ``_gap_certificate``: tv_dual_gap; out[0] is the regulariser's sum (``HuberChambollePock``: the
+        Huber sum, from tv_dual_gap_huber)"""
+        _nv.check(self.lib.tv_dual_gap(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]), _nv.ptr(b["qn"]),
+                                       _nv.ptr(self.x0), self.reg, float(qscale), out.data_ptr(), _nv.ptr(self.ws), self.stream))
 
     def _run_until_gap(self, rel_gap, max_n, check_every):
         """``run`` in blocks of ``check_every`` until gap <= rel_gap * max(|primal|, tiny) at a check or ``max_n`` iterations are done."""
@@ -1171,10 +1193,14 @@ class _ExtrapolatedCP(_SlabProblem):
         s, pl = self.slab, self.plan
         if pl.on:           # (no plane travels otherwise: at launch-bound sizes the two empty exchanges are host time worth skipping)
             s.wait(pl.exchange_image(self.x_bar, self.xh_prev, self.xh_next))
-        _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
-                                      sigma, self.reg, out[0:1].data_ptr(), _nv.ptr(self.ws), self.stream))
+        self._dual_kernel(sigma, out[0:1].data_ptr())
         if pl.on:
             s.wait(pl.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next)))
+
+    def _dual_kernel(self, sigma, out_ptr):
+        """the dual entry point of ``_dual_half``: tv_cp_dual (plain TV); ``HuberChambollePock`` has its own"""
+        _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
+                                      sigma, self.reg, out_ptr, _nv.ptr(self.ws), self.stream))
 
     def run_steps(self, rows):
         """Enqueue ``len(rows)`` iterations, row k of the (n, SLOTS) fp64 device tensor ``rows`` (zero on entry) receiving the scalars of
@@ -1214,7 +1240,8 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
     The scalars of iteration k are host doubles passed to the launches.  Not built: hipGraph capture, a device-resident step table, the
     placement tuner / arena of ``ChambollePock``, a persistent small-volume form, and the sweep / exchange / fix-up schedule of a sharded slab
     (slabs run the kernel pair) -- at the reference's small shapes the solver pays a launch per kernel against the persistent loop of
-    ``ChambollePock``.
+    ``ChambollePock`` (DESIGN.md section 3.4).  The Huber-TV regulariser (quadratic below a gradient magnitude alpha, against staircasing;
+    linearly convergent) is ``HuberChambollePock``.
 
     gamma = 0 gives theta = 1 and constant steps (Algorithm 1 with extrapolation).  The step schedule continues across ``run`` /
     ``run_steps`` / ``step`` calls (``self.it`` counts the iterations done); ``reset()`` starts it again.
@@ -1319,6 +1346,109 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
 
 
 # =================================================================================================
+class HuberChambollePock(_ExtrapolatedCP):
+    """min_x 1/2 |x - x0|^2 + regularization * sum_sites h_alpha(|D x|_2) -- the HUBER-TV (Huber-ROF) model of Chambolle & Pock 2011, section
+    6.2.1, the standard remedy for the staircasing of plain TV (smooth ramps coming back as terraces):
+
+        h_alpha(t) = t^2 / (2 alpha)  for t <= alpha,     t - alpha / 2  beyond
+
+    ``alpha`` is the gradient magnitude below which the model smooths instead of preserving an edge, in grey levels per weighted difference
+    (the differences D takes: per pixel, times sqrt(reg_z_over_reg) / sqrt(reg_time) along z / t).  It scales with the data's grey levels.
+
+    The quadratic part makes the conjugate of the regulariser (alpha / regularization)-strongly convex; the fidelity is 1-strongly convex.
+    Both halves of the saddle problem being strongly convex, Algorithm 3 of the paper applies: FIXED steps from ``cp_linear_steps(L2, gamma,
+    alpha / regularization)``, theta < 1, linear convergence O(omega^k).  State: x, x_bar (images), q (gradient); x = x_bar = x0, q = 0 at
+    the start.  One iteration:
+
+        v      = (q + sigma D x_bar) / (1 + sigma alpha / reg)
+        q     <- v / max(1, |v|_2 / reg)                                            tv_cp_dual_huber on x_bar  (2 Nd + 1 words per voxel)
+        x_new <- (x - tau D^T q + tau x0) / (1 + tau)
+        x_bar <- x_new + theta (x_new - x);  x <- x_new                             tv_cp_primal_accel, one pass (Nd + 4)
+
+    -- the kernel pair of ``AcceleratedChambollePock`` with another dual epilogue: 3 Nd + 5 words per voxel.  Sharded (``slab``): the boundary
+    plane(s) of x_bar travel before the dual kernel and those of q before the primal kernel, both waits exposed.
+
+    The model has an EXACT duality gap (``duality_gap``, ``run_until``), as the plain-TV solvers have.
+
+    alpha -> 0 makes mu -> 0 (tau -> 0, sigma -> inf): the linear rate degenerates, and ``AcceleratedChambollePock`` -- plain TV, O(1/k^2)
+    -- is then the solver to use.  alpha = 0 is refused.
+
+    Not built (out of scope here): a one-sweep / fix-up form of this iteration, a persistent small-volume form, hipGraph capture, the
+    placement tuner / arena of ``ChambollePock``, a plane-marching form of the gap kernel, and Huber-TV under the L1 / Huber / KL data terms
+    of ``RobustChambollePock`` / ``PoissonChambollePock``.
+
+    Per-step scalars: the slots of ``ChambollePock`` -- sum h_alpha(|D x_bar|_2) in slot 0, 1/2 |x_new - x0|^2 in slot ``F``."""
+
+    def __init__(self, x0, regularization, alpha, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
+                 factor_reg_static=0, gamma=1.0, slab=None, pitch="auto"):
+        """alpha: see the class docstring; finite and > 0, as is ``regularization``.  gamma: the strong-convexity constant of the fidelity the
+        steps are computed for, 0 < gamma <= 1 (1.0 = its true value; smaller = more conservative steps).  ValueError otherwise.  pitch: see
+        ``_SlabProblem``."""
+        alpha, gamma = float(alpha), float(gamma)
+        if not (math.isfinite(alpha) and alpha > 0.0):
+            raise ValueError("HuberChambollePock: alpha must be finite and > 0 (alpha = 0 is plain TV: AcceleratedChambollePock)")
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError("HuberChambollePock: gamma must be in (0, 1]")
+        if not (math.isfinite(float(regularization)) and float(regularization) > 0.0):
+            raise ValueError("HuberChambollePock: regularization must be finite and > 0")
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
+        self.alpha, self.gamma = alpha, gamma
+        self.tau, self.sigma, self.theta, self.mu = cp_linear_steps(self.L2, gamma, alpha / self.reg)
+        self._alloc_state()
+
+    def _dual_kernel(self, sigma, out_ptr):
+        _nv.check(self.lib.tv_cp_dual_huber(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
+                                            sigma, self.reg, self.alpha, out_ptr, _nv.ptr(self.ws), self.stream))
+
+    def step(self, out=None):
+        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's sum h_alpha(|D x_bar|_2) in
+        slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch."""
+        out = self._scratch if out is None else out
+        F = self.F
+        self._dual_half(self.sigma, out)
+        _nv.check(self.lib.tv_cp_primal_accel(self.geo.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x),
+                                              _nv.ptr(self.x_bar), _nv.ptr(self.x0), self.tau, self.theta, out[F:F + 1].data_ptr(),
+                                              _nv.ptr(self.ws), self.stream))
+        self.it += 1
+
+    def run(self, n_iter, record_loss=True):
+        """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
+        None.  Row k is 1/2 |x_{k+1} - x0|^2 + reg * sum h_alpha(|D x_bar_k|_2): the regulariser is that of the EXTRAPOLATED point the dual
+        step saw -- a progress indicator in the slots of ``ChambollePock``'s history.  The exact primal value of the current iterate is
+        ``duality_gap()[0]``."""
+        return self._run(n_iter, record_loss)
+
+    _GAP_DOC = """For P(x) = 1/2 |x - x0|^2 + reg sum h_alpha(|D x|_2) and any dual variable q with |q|_2 <= reg per site,
+        Dual(q) = <D^T q, x0> - 1/2 |D^T q|^2 - (alpha / 2 reg) |q|^2 <= P(x*) <= P(x), and by strong convexity 1/2 |x - x*|^2 <= P(x) - Dual(q).
+        The kernel (tv_dual_gap_huber) sums the gap site by site as 1/2 (x - x0 + D^T q)^2 + [reg h_alpha(|D x|_2) - <q, D x> + (alpha / 2 reg)
+        |q|^2], both parts >= 0 (the second as a perfect square where |D x|_2 <= alpha), and writes nothing but three scalars.
+        fp32 FLOOR: beyond alpha the second part cancels, leaving an absolute error of order eps_fp32 * P, so relative gaps below about 1e-6
+        are not resolvable in fp32; the gap may then come out slightly negative (it is not clamped) and ``run_until`` ends on its iteration
+        limit with ``converged=False``."""
+
+    def _gap_kernel(self, x, q, qscale, b, out):
+        _nv.check(self.lib.tv_dual_gap_huber(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]),
+                                             _nv.ptr(b["qn"]), _nv.ptr(self.x0), self.reg, self.alpha, out.data_ptr(), _nv.ptr(self.ws),
+                                             self.stream))
+
+    def duality_gap(self):
+        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+        calls; the state of the loop is not touched (halo buffers of its own, one all-reduce of three scalars).  primal = 1/2 |x - x0|^2 +
+        reg * sum h_alpha(|D x|_2).  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._gap_certificate(self.x, self.q, 1.0)
+    duality_gap.__doc__ += _GAP_DOC
+
+    def run_until(self, rel_gap, max_iter, check_every=10):
+        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
+        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
+        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
+        """
+        return self._run_until_gap(rel_gap, max_iter, check_every)
+    run_until.__doc__ += _GAP_DOC
+
+
+# =================================================================================================
 class _FixedPointResiduals:
     """The optimality residual of the solvers whose fidelity has a pointwise prox but no cheap duality gap (``RobustChambollePock``,
     ``PoissonChambollePock``): tv_cp_dual_residual for the dual block, the class's primal kernel in residual mode for the fidelity block.
@@ -1386,7 +1516,7 @@ class RobustChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
 
     Not built (out of scope here): a one-sweep / fix-up form of the iteration, hipGraph capture, a persistent small-volume form, the placement
     tuner / arena of ``ChambollePock``.  The Poisson / Kullback-Leibler fidelity (a pointwise prox with a square root and positivity
-    handling of its own) is ``PoissonChambollePock``.
+    handling of its own) is ``PoissonChambollePock``; the Huber-TV REGULARISER (with the quadratic data term) is ``HuberChambollePock``.
 
     Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, F(x_new - x0) in slot ``F``."""
 
@@ -1488,7 +1618,7 @@ class PoissonChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
     1 + D^T q > 0 at every site, which the iterates do not guarantee.)
 
     Not built: a one-sweep / fix-up form of the iteration, hipGraph capture, a persistent small-volume form, the placement tuner / arena
-    of ``ChambollePock``, and a background term.
+    of ``ChambollePock``, and a background term.  The Huber-TV regulariser exists for the quadratic data term only (``HuberChambollePock``).
 
     Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, F(x_new) in slot ``F``."""
 

@@ -36,7 +36,10 @@ def _one_pass(pytv, x, scheme, **kw):
     return float(tv), G
 
 
-# tile geometry of the kernel: 14 useful rows x 56 useful columns per block, ring of one row / one 4-column vector
+# tile geometry of the kernel (k_subgrad_col): a block stores 14 rows x 120 / 124 columns (fp32 hybrid, central / upwind, downwind
+# without the aligned tiles), 30 x 64 (fp32 aligned tiles), 6 x 60 / 62 (fp64) or 14 x 64 (fp64 aligned); none of the frames below
+# has a tile strictly inside it, so all of them run the generic body: interior_rect() of test_gpu_subgrad_interior.py restates the
+# rule, and that file holds the frames that reach the interior and column-border bodies
 @pytest.mark.parametrize("scheme", ONE_PASS_SCHEMES)
 @pytest.mark.parametrize("zchunk", ["0", "3"])
 @pytest.mark.parametrize("shape,lz,mu,use_mask", [

@@ -7,6 +7,8 @@
 //   g_options, env_int           the option table
 //   plane_big_enough, march_ok   which kernel family a geometry takes
 //   check_x_halos[2], check_y_halos   halo rules
+//   finite_pos, finite_in_01     scalar rules
+//   Call, pick_store             one D / D^T launch; run-time store flag -> epilogue template
 //   namespace tvm                launchers defined in the other translation units
 #pragma once
 #include <hip/hip_runtime.h>
@@ -162,7 +164,17 @@ struct Partials {
         HIP_TRY(hipGetLastError());
         return 0;
     }
+    // results[k] = sum of the first n partials of slot k, for the slots 0 .. slots-1 (kernels that keep several sums on one grid)
+    int reduce_n(int slots, long long n, double* results, hipStream_t st) const {
+        for (int k = 0; k < slots; ++k)
+            if (int rc = reduce(k, n, results + k, st)) return rc;
+        return 0;
+    }
 };
+
+// argument rules that several entry points share (each keeps its own error text)
+inline bool finite_pos(double v) { return std::isfinite(v) && v > 0.0; }
+inline bool finite_in_01(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
 
 inline bool aligned16(std::initializer_list<const void*> ps) {
     for (const void* p : ps)
@@ -320,16 +332,39 @@ inline int check_y_halos(const tv_geom* g, const DG& d, const void* yp, const vo
 }
 
 // ---- plane-marching launchers, defined in tv_march_D.hip / tv_march_DT.hip ---------------------------
+// One launch of the forward (D) or transposed (D^T) stencil with an epilogue: what every launcher of either kernel form takes.
+struct Call {
+    const tv_geom* g;
+    const DG& d;
+    const void *c, *prev, *next;      // the array the stencil reads (x for D, the gradient for D^T) and its two halo planes
+    hipStream_t st;
+    long long nblocks = 0;            // out: the blocks launched, each of which wrote one partial sum per reducing epilogue
+};
+// run-time store flag -> one of two <typename, int> epilogue templates: f.template operator()<On or Off>()
+template <template <typename, int> class On, template <typename, int> class Off, typename F> inline int pick_store(bool store, F&& f) {
+    return store ? f.template operator()<On>() : f.template operator()<Off>();
+}
+// M = 16 of the schemes with a 16-frame-wide working set (central, hybrid): there an 8-vector epilogue of the marching forward kernel spills
+// (CpDual: 164 / 340 bytes of scratch per lane).  CpDualHuber is not instantiated for these: launch_D_march leaves them out and
+// tv_cp_dual_huber keeps them on the one-site kernel, both by this ONE rule.
+constexpr bool wide16(int scheme, int m) { return m == 16 && (scheme == CENTRAL || scheme == HYBRID); }
+
+namespace tv {      // the epilogue argument structs of tv_stencil.h
+template <typename T> struct StoreDArgs; template <typename T> struct CpDualArgs; template <typename T> struct CpDualHuberArgs;
+template <typename T> struct AdmmZUArgs; template <typename T> struct GapDArgs; template <typename T> struct StoreDTArgs;
+template <typename T> struct AxpyDTArgs; template <typename T> struct CpPrimalArgs; template <typename T> struct CpPrimalAccelArgs;
+template <typename T> struct CpPrimalProxArgs; template <typename T> struct CpPrimalKLArgs; template <typename T> struct GapDTArgs;
+}
 namespace tvm {
-int D_store(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb, float* dout);
-int D_cp_dual(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-              float* q, float sigma, float inv_lambda, double* partials);
-// the same for the Huber-TV regulariser (tv_cp_dual_huber; CpDualHuber of tv_stencil.h): sum h_alpha(|D x|_2) instead of |D x|_{2,1}.
-// Not (central / hybrid, M = 16): those instantiations would use scratch and are left out -- D_cp_dual_huber_ok answers false, the
-// one-site kernel does the work
-bool D_cp_dual_huber_ok(const tv_geom* g, const DG& d);
-int D_cp_dual_huber(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-                    float* q, float sigma, float shrink, float inv_lambda, double alpha, double half_inv_alpha, double* partials);
+// D x with the epilogue whose arguments are given (fp32): one overload per epilogue, each a line in tv_march_D.hip
+int D_march(Call& c, const StoreDArgs<float>& a);
+int D_march(Call& c, const CpDualArgs<float>& a);
+int D_march(Call& c, const CpDualHuberArgs<float>& a);       // not where wide16(scheme, M)
+int D_march(Call& c, const AdmmZUArgs<float>& a);
+// duality gap, reduce-only (tv_dual_gap): the D^T-side pass (DT_march with GapDTArgs) writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2,
+// the D-side pass (same grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to
+// the first pass's sums
+int D_march(Call& c, const GapDArgs<float>& a);
 // sub-gradient passes on the marching path: pass 1 = |Dx| (0 -> +inf) on the local planes plus ghost planes,
 // pass 2 = G from x and |Dx| (radius-1 schemes only); x halo buffers hold TWO planes each
 int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
@@ -340,8 +375,6 @@ bool subgrad_pass2_ok(const tv_geom* g, const DG& d);
 // x + rho D^T D x (radius-1 schemes, M <= 8): LIGHT marching kernel with the hybrid stencil; two-plane halo buffers
 int D_normal_op(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
                 float* out, float rho, double* partials);
-int D_admm_zu(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-              float* z, float* u, float thresh, double* partials, int tform);
 // streaming normal operator (tv_nstream.h): radius-1 schemes, fp32; two dot products
 bool N_stream_ok(const tv_geom* g, const DG& d, bool vec);
 // optional Chebyshev form of the epilogue (tv_cheb_step): out = [add +] x + alpha (b - A x) + beta (x - y)
@@ -351,28 +384,19 @@ int N_stream(const tv_geom* g, const DG& d, const void* x, const void* xp, const
 // streaming forward kernel (tv_dstream.h): d = D x without LDS tile or barrier, every load one plane ahead of its use
 bool D_stream_ok(const tv_geom* g, const DG& d, bool vec);
 int D_stream(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, void* dout);
-// (fp32 and fp64: the arrays are of g->dtype)
-int DT_store(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb, void* out);
-int DT_axpy(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
-            void* out, const void* base, double alpha, const void* base2 = nullptr, double beta = 0.0);
-int DT_cp_primal(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
-                 float* x, const float* x0, float* p, float tau, float sigma_a, float inv_1p_sigma_a, double* partials);
+// D^T q with the epilogue whose arguments are given: one overload per epilogue and element type, each a line in tv_march_DT.hip.  fp64
+// exists for the plain store and the axpy only (march_dt_ok)
+int DT_march(Call& c, const StoreDTArgs<float>& a);
+int DT_march(Call& c, const StoreDTArgs<double>& a);
+int DT_march(Call& c, const AxpyDTArgs<float>& a);
+int DT_march(Call& c, const AxpyDTArgs<double>& a);
+int DT_march(Call& c, const CpPrimalArgs<float>& a);
 // accelerated primal step (tv_cp_primal_accel): x, x0 read once, x and x_bar written once -- Nd + 4 words per voxel
-int DT_cp_primal_accel(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
-                       float* x, float* x_bar, const float* x0, float tau, float inv_1p_tau, float theta, double* partials);
+int DT_march(Call& c, const CpPrimalAccelArgs<float>& a);
 // primal step with a pointwise prox (tv_cp_primal_prox; CpPrimalProxT of tv_stencil.h): store = the step (Nd + 4 words per voxel), !store = the
 // reduce-only residual (Nd + 2; x_bar is not touched and may be NULL)
-int DT_cp_primal_prox(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
-                      bool store, float* x, float* x_bar, const float* x0, float tau, float theta, float c, float t, double cap,
-                      double half_inv, double inv_tau, double* partials);
+int DT_march(Call& c, const CpPrimalProxArgs<float>& a, bool store);
 // primal step for the Poisson / Kullback-Leibler data term (tv_cp_primal_kl; CpPrimalKLT of tv_stencil.h): store / !store as above
-int DT_cp_primal_kl(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
-                    bool store, float* x, float* x_bar, const float* x0, float tau, float theta, float two_tau, float four_tau,
-                    double inv_tau, double* partials);
-// duality gap, reduce-only (tv_dual_gap): the D^T-side pass writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2, the D-side pass (same
-// grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to the first pass's sums
-int DT_gap(const tv_geom* g, const DG& d, const void* q, const void* qp, const void* qn, hipStream_t st, long long* nb,
-           const float* x, const float* x0, float qscale, double* partials);
-int D_gap(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-          const float* q, const float* x0, float qscale, double lambda, double* p_tv, double* p_fid, double* p_gap);
+int DT_march(Call& c, const CpPrimalKLArgs<float>& a, bool store);
+int DT_march(Call& c, const GapDTArgs<float>& a);             // (see D_march with GapDArgs)
 }  // namespace tvm

@@ -754,6 +754,47 @@ static int launch_subgrad_vec(const tv_geom* g, const DG& d, const void* x, cons
     return 0;
 }
 
+// ---- the two runners of the epilogue entry points -------------------------------------------------------------------------------
+// An entry point makes its checks, forms its constants in double and hands over: the Call, whether the 16-byte-lane kernels may run
+// (`vec`), whether the plane-marching form may (`march`), and `args`, a generic lambda that builds the epilogue's XArgs<T> for the element
+// type T -- the ONE place where the epilogue's fields are named.  site_D / site_DT launch the one-site kernel; run_D / run_DT launch the
+// marching overload (fp32) or the one-site kernel and then reduce slot 0 of the partials, one per block, into *result.
+template <template <int, typename, int> class EpiT, typename MakeArgs> static int site_D(Call& c, bool vec, MakeArgs&& args) {
+    return dispatch(c.g->scheme, c.g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        const LC lc = launch_cfg(c.d, V, c.d.nz);
+        c.nblocks = lc.nblocks;
+        EpiT<S, T, V> epi{args.template operator()<T>()};
+        hipLaunchKernelGGL((k_D<S, T, V, EpiT<S, T, V>>), lc.grid, lc.block, 0, c.st, c.d, make_w<T>(c.g), (const T*)c.c, (const T*)c.prev,
+                           (const T*)c.next, 1, 0, epi);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+}
+template <template <int, typename, int> class EpiT, typename MakeArgs>
+static int run_D(Call& c, bool vec, bool march, MakeArgs&& args, const Partials& P, double* result) {
+    if (int rc = march ? tvm::D_march(c, args.template operator()<float>()) : site_D<EpiT>(c, vec, args)) return rc;
+    return P.reduce(0, c.nblocks, result, c.st);
+}
+// Src: how the gather reads the gradient.  SrcPlain {c.c, halos}; SrcDiff takes the array to subtract as `more`: {c.c, more, halos}
+template <template <typename, int> class EpiT, template <typename, int> class Src = SrcPlain, typename MakeArgs, typename... More>
+static int site_DT(Call& c, bool vec, MakeArgs&& args, More... more) {
+    return dispatch(c.g->scheme, c.g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        const LC lc = launch_cfg(c.d, V, c.d.nz);
+        c.nblocks = lc.nblocks;
+        Src<T, V> src{(const T*)c.c, (const T*)more..., (const T*)c.prev, (const T*)c.next};
+        EpiT<T, V> epi{args.template operator()<T>()};
+        hipLaunchKernelGGL((k_DT<S, T, V, Src<T, V>, EpiT<T, V>>), lc.grid, lc.block, 0, c.st, c.d, make_w<T>(c.g), src, epi);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+}
+// store...: the run-time flag that the marching overloads of the STORE / reduce-only epilogue pairs take (EpiT is the one pick_store chose)
+template <template <typename, int> class EpiT, typename MakeArgs, typename... Store>
+static int run_DT(Call& c, bool vec, bool march, MakeArgs&& args, const Partials& P, double* result, Store... store) {
+    if (int rc = march ? tvm::DT_march(c, args.template operator()<float>(), store...) : site_DT<EpiT>(c, vec, args)) return rc;
+    return P.reduce(0, c.nblocks, result, c.st);
+}
+
 extern "C" {
 
 const char* tv_last_error(void) { return g_err.c_str(); }
@@ -804,18 +845,10 @@ int tv_D(const tv_geom* g, const void* x, const void* x_prev, const void* x_next
     const int kern = env_int("TV_D_KERNEL", env_int("TV_MARCH_D", 0) ? 1 : (big_plane ? 2 : 0));
     if (kern == 2 && tvm::D_stream_ok(g, d, vec) && !env_int("TV_NO_MARCH", 0))
         return tvm::D_stream(g, d, x, x_prev, x_next, st, dout);
-    if (kern == 1 && march_ok(g, d, vec)) {
-        long long nb;
-        return tvm::D_store(g, d, x, x_prev, x_next, st, &nb, (float*)dout);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        StoreD<S, T, V> epi{(T*)dout, nullptr};
-        hipLaunchKernelGGL((k_D<S, T, V, StoreD<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
-                           (const T*)x_prev, (const T*)x_next, 1, 0, epi);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    });
+    Call c{g, d, x, x_prev, x_next, st};
+    auto args = [&]<typename T>() { return StoreDArgs<T>{(T*)dout, nullptr}; };
+    if (kern == 1 && march_ok(g, d, vec)) return tvm::D_march(c, args.template operator()<float>());
+    return site_D<StoreD>(c, vec, args);
 }
 
 int tv_DT(const tv_geom* g, const void* y, const void* y_prev, const void* y_next, void* out, void* stream) {
@@ -836,31 +869,15 @@ int tv_DT_axpy2(const tv_geom* g, const void* a, const void* b, const void* ab_p
     const bool vec = rows_vectorisable(g, d) && aligned16({a, b, ab_prev, ab_next, base, base2, out, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const bool plain_store = (base == nullptr && base2 == nullptr && alpha == 1.0);
-    if (b == nullptr && march_dt_ok(g, d, vec, plain_store)) {          // plane-marching adjoint (tv_march.h): fp32, and since round 4 fp64 hybrid tv_DT
-        long long nb;
-        if (plain_store) return tvm::DT_store(g, d, a, ab_prev, ab_next, st, &nb, out);
-        return tvm::DT_axpy(g, d, a, ab_prev, ab_next, st, &nb, out, base, alpha, base2, beta);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        WT<T> w = make_w<T>(g);
-        if (b == nullptr) {
-            SrcPlain<T, V> src{(const T*)a, (const T*)ab_prev, (const T*)ab_next};
-            if (plain_store) {
-                StoreDT<T, V> epi{(T*)out, nullptr};
-                hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, StoreDT<T, V>>), lc.grid, lc.block, 0, st, d, w, src, epi);
-            } else {
-                AxpyDT<T, V> epi{(T*)out, (const T*)base, (T)alpha, nullptr, (const T*)base2, (T)beta};
-                hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, AxpyDT<T, V>>), lc.grid, lc.block, 0, st, d, w, src, epi);
-            }
-        } else {
-            SrcDiff<T, V> src{(const T*)a, (const T*)b, (const T*)ab_prev, (const T*)ab_next};
-            AxpyDT<T, V> epi{(T*)out, (const T*)base, (T)alpha, nullptr, (const T*)base2, (T)beta};
-            hipLaunchKernelGGL((k_DT<S, T, V, SrcDiff<T, V>, AxpyDT<T, V>>), lc.grid, lc.block, 0, st, d, w, src, epi);
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
-    });
+    Call c{g, d, a, ab_prev, ab_next, st};
+    auto store = [&]<typename T>() { return StoreDTArgs<T>{(T*)out, nullptr}; };
+    auto axpy = [&]<typename T>() { return AxpyDTArgs<T>{(T*)out, (const T*)base, (T)alpha, nullptr, (const T*)base2, (T)beta}; };
+    if (b == nullptr && march_dt_ok(g, d, vec, plain_store))            // plane-marching adjoint (tv_march.h): fp32, and since round 4 fp64 hybrid tv_DT
+        return dispatch_dtype(g->dtype, [&]<typename T>() -> int {
+            return plain_store ? tvm::DT_march(c, store.template operator()<T>()) : tvm::DT_march(c, axpy.template operator()<T>());
+        });
+    if (b != nullptr) return site_DT<AxpyDT, SrcDiff>(c, vec, axpy, b);
+    return plain_store ? site_DT<StoreDT>(c, vec, store) : site_DT<AxpyDT>(c, vec, axpy);
 }
 
 int tv_l21(const tv_geom* g, const void* dimg, int32_t nd, void* norms, double* result, void* ws, void* stream) {
@@ -984,24 +1001,14 @@ int tv_cp_dual(const tv_geom* g, const void* x, const void* x_prev, const void* 
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);
-    if (march_ok(g, d, vec)) {
-        long long nb;
-        if (int rc = tvm::D_cp_dual(g, d, x, x_prev, x_next, st, &nb, (float*)q, (float)sigma_D, (float)(1.0 / lambda), P.slot(0))) return rc;
-        return P.reduce(0, nb, tvout, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        CpDual<S, T, V> epi{(T*)q, (T)sigma_D, (T)(1.0 / lambda), P.slot(0)};
-        hipLaunchKernelGGL((k_D<S, T, V, CpDual<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
-                           (const T*)x_prev, (const T*)x_next, 1, 0, epi);
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, tvout, st);
-    });
+    Call c{g, d, x, x_prev, x_next, st};
+    return run_D<CpDual>(c, vec, march_ok(g, d, vec), [&]<typename T>() {
+        return CpDualArgs<T>{(T*)q, (T)sigma_D, (T)(1.0 / lambda), P.slot(0)};
+    }, P, tvout);
 }
 
 // Dual step for the Huber-TV regulariser (include/pytv4d.h): tv_cp_dual's halo, alignment and launch rules with the CpDualHuber epilogue.
 // shrink = 1 / (1 + sigma alpha / lambda) and 1 / (2 alpha) are formed here in double; every argument check precedes the first device access.
-static inline bool finite_pos(double v) { return std::isfinite(v) && v > 0.0; }
 int tv_cp_dual_huber(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q, double sigma_D,
                      double lambda, double alpha, double* hubout, void* ws, void* stream) {
     DG d;
@@ -1015,20 +1022,10 @@ int tv_cp_dual_huber(const tv_geom* g, const void* x, const void* x_prev, const 
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);
     const double shrink = 1.0 / (1.0 + sigma_D * alpha / lambda), inv_lambda = 1.0 / lambda, half_inv_alpha = 0.5 / alpha;
-    if (march_ok(g, d, vec) && tvm::D_cp_dual_huber_ok(g, d)) {
-        long long nb;
-        if (int rc = tvm::D_cp_dual_huber(g, d, x, x_prev, x_next, st, &nb, (float*)q, (float)sigma_D, (float)shrink, (float)inv_lambda, alpha,
-                                          half_inv_alpha, P.slot(0))) return rc;
-        return P.reduce(0, nb, hubout, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        CpDualHuber<S, T, V> epi{(T*)q, (T)sigma_D, (T)shrink, (T)inv_lambda, alpha, half_inv_alpha, P.slot(0)};
-        hipLaunchKernelGGL((k_D<S, T, V, CpDualHuber<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
-                           (const T*)x_prev, (const T*)x_next, 1, 0, epi);
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, hubout, st);
-    });
+    Call c{g, d, x, x_prev, x_next, st};
+    return run_D<CpDualHuber>(c, vec, march_ok(g, d, vec) && !wide16(g->scheme, d.m), [&]<typename T>() {
+        return CpDualHuberArgs<T>{(T*)q, (T)sigma_D, (T)shrink, (T)inv_lambda, alpha, half_inv_alpha, P.slot(0)};
+    }, P, hubout);
 }
 
 int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, const void* x0,
@@ -1041,20 +1038,10 @@ int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void
     const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x0, p, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);
-    if (march_ok(g, d, vec)) {
-        long long nb;
-        if (int rc = tvm::DT_cp_primal(g, d, q, q_prev, q_next, st, &nb, (float*)x, (const float*)x0, (float*)p, (float)tau,
-                                               (float)sigma_A, (float)(1.0 / (1.0 + sigma_A)), P.slot(0))) return rc;
-        return P.reduce(0, nb, fid, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
-        CpPrimal<T, V> epi{(T*)x, (const T*)x0, (T*)p, (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), P.slot(0)};
-        hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimal<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, fid, st);
-    });
+    Call c{g, d, q, q_prev, q_next, st};
+    return run_DT<CpPrimal>(c, vec, march_ok(g, d, vec), [&]<typename T>() {
+        return CpPrimalArgs<T>{(T*)x, (const T*)x0, (T*)p, (T)tau, (T)sigma_A, (T)(1.0 / (1.0 + sigma_A)), P.slot(0)};
+    }, P, fid);
 }
 
 // Accelerated Chambolle-Pock primal step with the extrapolation folded in (include/pytv4d.h): tv_cp_primal's gather and launch rules with
@@ -1066,27 +1053,17 @@ int tv_cp_primal_accel(const tv_geom* g, const void* q, const void* q_prev, cons
     if (q == nullptr || x == nullptr || x_bar == nullptr || x0 == nullptr || fid == nullptr || ws == nullptr)
         return fail(TV_E_ARG, "NULL array");
     if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
-    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
-    if (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (!finite_pos(tau)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (!finite_in_01(theta)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
     if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);
     const double inv_1p_tau = 1.0 / (1.0 + tau);
-    if (march_ok(g, d, vec)) {
-        long long nb;
-        if (int rc = tvm::DT_cp_primal_accel(g, d, q, q_prev, q_next, st, &nb, (float*)x, (float*)x_bar, (const float*)x0, (float)tau,
-                                             (float)inv_1p_tau, (float)theta, P.slot(0))) return rc;
-        return P.reduce(0, nb, fid, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
-        CpPrimalAccel<T, V> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)inv_1p_tau, (T)theta, P.slot(0)};
-        hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalAccel<T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, fid, st);
-    });
+    Call c{g, d, q, q_prev, q_next, st};
+    return run_DT<CpPrimalAccel>(c, vec, march_ok(g, d, vec), [&]<typename T>() {
+        return CpPrimalAccelArgs<T>{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)inv_1p_tau, (T)theta, P.slot(0)};
+    }, P, fid);
 }
 
 // Chambolle-Pock primal step with a pointwise prox of the fidelity (L2 / L1 / Huber), or its reduce-only fixed-point residual
@@ -1102,9 +1079,9 @@ int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const
     if (q == nullptr || x == nullptr || x0 == nullptr || out == nullptr || ws == nullptr || (store && x_bar == nullptr))
         return fail(TV_E_ARG, "NULL array");
     if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
-    if (fidelity == TV_FID_HUBER && (!std::isfinite(delta) || !(delta > 0.0))) return fail(TV_E_ARG, "delta must be a finite number > 0");
-    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
-    if (store && (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0))) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (fidelity == TV_FID_HUBER && !finite_pos(delta)) return fail(TV_E_ARG, "delta must be a finite number > 0");
+    if (!finite_pos(tau)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (store && !finite_in_01(theta)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
     if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, d.wv});
     hipStream_t st = (hipStream_t)stream;
@@ -1116,23 +1093,12 @@ int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const
     const double cap = fidelity == TV_FID_L1 ? 0.0 : (fidelity == TV_FID_HUBER ? delta : inf);
     const double half_inv = fidelity == TV_FID_L1 ? 0.0 : (fidelity == TV_FID_HUBER ? 0.5 / delta : 0.5);
     const double th = store ? theta : 0.0, inv_tau = 1.0 / tau;
-    if (march_ok(g, d, vec)) {
-        long long nb;
-        if (int rc = tvm::DT_cp_primal_prox(g, d, q, q_prev, q_next, st, &nb, store, (float*)x, (float*)x_bar, (const float*)x0, (float)tau,
-                                            (float)th, (float)c, (float)t, cap, half_inv, inv_tau, P.slot(0))) return rc;
-        return P.reduce(0, nb, out, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
-        auto launch = [&]<bool STORE>() {
-            CpPrimalProxT<T, V, STORE> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)c, (T)t, cap, half_inv, inv_tau, P.slot(0)};
-            hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalProxT<T, V, STORE>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
-        };
-        if (store) launch.template operator()<true>();
-        else launch.template operator()<false>();
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, out, st);
+    Call call{g, d, q, q_prev, q_next, st};
+    auto args = [&]<typename T>() {
+        return CpPrimalProxArgs<T>{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)c, (T)t, cap, half_inv, inv_tau, P.slot(0)};
+    };
+    return pick_store<CpPrimalProx, CpPrimalProxRes>(store, [&]<template <typename, int> class E>() {
+        return run_DT<E>(call, vec, march_ok(g, d, vec), args, P, out, store);
     });
 }
 
@@ -1147,30 +1113,19 @@ int tv_cp_primal_kl(const tv_geom* g, const void* q, const void* q_prev, const v
     if (q == nullptr || x == nullptr || x0 == nullptr || out == nullptr || ws == nullptr || (store && x_bar == nullptr))
         return fail(TV_E_ARG, "NULL array");
     if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
-    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(TV_E_ARG, "tau must be a finite number > 0");
-    if (store && (!std::isfinite(theta) || !(theta >= 0.0 && theta <= 1.0))) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (!finite_pos(tau)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (store && !finite_in_01(theta)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
     if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);
     const double th = store ? theta : 0.0, two_tau = 2.0 * tau, four_tau = 4.0 * tau, inv_tau = 1.0 / tau;
-    if (march_ok(g, d, vec)) {
-        long long nb;
-        if (int rc = tvm::DT_cp_primal_kl(g, d, q, q_prev, q_next, st, &nb, store, (float*)x, (float*)x_bar, (const float*)x0, (float)tau,
-                                          (float)th, (float)two_tau, (float)four_tau, inv_tau, P.slot(0))) return rc;
-        return P.reduce(0, nb, out, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        SrcPlain<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next};
-        auto launch = [&]<bool STORE>() {
-            CpPrimalKLT<T, V, STORE> epi{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)two_tau, (T)four_tau, inv_tau, P.slot(0)};
-            hipLaunchKernelGGL((k_DT<S, T, V, SrcPlain<T, V>, CpPrimalKLT<T, V, STORE>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), src, epi);
-        };
-        if (store) launch.template operator()<true>();
-        else launch.template operator()<false>();
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, out, st);
+    Call c{g, d, q, q_prev, q_next, st};
+    auto args = [&]<typename T>() {
+        return CpPrimalKLArgs<T>{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)two_tau, (T)four_tau, inv_tau, P.slot(0)};
+    };
+    return pick_store<CpPrimalKL, CpPrimalKLRes>(store, [&]<template <typename, int> class E>() {
+        return run_DT<E>(c, vec, march_ok(g, d, vec), args, P, out, store);
     });
 }
 
@@ -1187,21 +1142,15 @@ int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void*
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, q_prev, q_next, x0, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);                              // slot 0: |D x|_{2,1}, slot 1: 1/2 |x - x0|^2, slot 2: the gap
-    auto reduce3 = [&](long long n) -> int {
-        for (int k = 0; k < 3; ++k)
-            if (int rc = P.reduce(k, n, out + k, st)) return rc;
-        return 0;
-    };
     if (march_ok(g, d, vec) && d.m <= 8) {
         // plane-marching form, two launches on the same grid: q is read by both (2 Nd + 5 words per voxel).  Not M = 16: the D-side
         // kernel keeps 16 frames and their q samples in flight and spills (288 - 1540 bytes of scratch per lane)
-        long long nb_dt, nb;
-        if (int rc = tvm::DT_gap(g, d, q, q_prev, q_next, st, &nb_dt, (const float*)x, (const float*)x0, (float)qscale, P.slot(2))) return rc;
-        if (int rc = tvm::D_gap(g, d, x, x_prev, x_next, st, &nb, (const float*)q, (const float*)x0, (float)qscale, lambda, P.slot(0), P.slot(1),
-                                  P.slot(2)))
+        Call cq{g, d, q, q_prev, q_next, st}, cx{g, d, x, x_prev, x_next, st};
+        if (int rc = tvm::DT_march(cq, GapDTArgs<float>{(const float*)x, (const float*)x0, (float)qscale, P.slot(2)})) return rc;
+        if (int rc = tvm::D_march(cx, GapDArgs<float>{(const float*)q, (const float*)x0, (float)qscale, lambda, P.slot(0), P.slot(1), P.slot(2)}))
             return rc;
-        if (nb != nb_dt) return fail(TV_E_ARG, "tv_dual_gap: the two marching passes disagree about the grid");
-        return reduce3(nb);
+        if (cx.nblocks != cq.nblocks) return fail(TV_E_ARG, "tv_dual_gap: the two marching passes disagree about the grid");
+        return P.reduce_n(3, cx.nblocks, out, st);
     }
     return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
         LC lc = launch_cfg(d, V, d.nz);
@@ -1209,7 +1158,7 @@ int tv_dual_gap(const tv_geom* g, const void* x, const void* x_prev, const void*
         hipLaunchKernelGGL((k_gap<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
                            src, (const T*)x0, lambda, P.slot(0), P.slot(1), P.slot(2));
         HIP_TRY(hipGetLastError());
-        return reduce3(lc.nblocks);
+        return P.reduce_n(3, lc.nblocks, out, st);
     });
 }
 
@@ -1234,9 +1183,7 @@ int tv_dual_gap_huber(const tv_geom* g, const void* x, const void* x_prev, const
         hipLaunchKernelGGL((k_gap_huber<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
                            src, (const T*)x0, k, P.slot(0), P.slot(1), P.slot(2));
         HIP_TRY(hipGetLastError());
-        for (int s = 0; s < 3; ++s)
-            if (int rc = P.reduce(s, lc.nblocks, out + s, st)) return rc;
-        return 0;
+        return P.reduce_n(3, lc.nblocks, out, st);
     });
 }
 
@@ -1248,7 +1195,7 @@ int tv_cp_dual_residual(const tv_geom* g, const void* x, const void* x_prev, con
     if (int rc = make_dg(g, d, true)) return rc;
     if (x == nullptr || q == nullptr || out == nullptr || ws == nullptr) return fail(TV_E_ARG, "NULL array");
     if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
-    if (!(sigma_D > 0.0) || !std::isfinite(sigma_D)) return fail(TV_E_ARG, "sigma_D must be a finite number > 0");
+    if (!finite_pos(sigma_D)) return fail(TV_E_ARG, "sigma_D must be a finite number > 0");
     if (int rc = check_x_halos(g, d, x_prev, x_next)) return rc;
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, d.wv});
     hipStream_t st = (hipStream_t)stream;
@@ -1258,8 +1205,7 @@ int tv_cp_dual_residual(const tv_geom* g, const void* x, const void* x_prev, con
         hipLaunchKernelGGL((k_cp_res<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
                            (const T*)q, (T)sigma_D, (T)(1.0 / lambda), 1.0 / (sigma_D * sigma_D), P.slot(0), P.slot(1));
         HIP_TRY(hipGetLastError());
-        if (int rc = P.reduce(0, lc.nblocks, out, st)) return rc;
-        return P.reduce(1, lc.nblocks, out + 1, st);
+        return P.reduce_n(2, lc.nblocks, out, st);
     });
 }
 
@@ -1272,19 +1218,10 @@ static int admm_zu_impl(const tv_geom* g, const void* x, const void* x_prev, con
     const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, z, u, d.wv});
     hipStream_t st = (hipStream_t)stream;
     const Partials P(ws, d);
-    if (march_ok(g, d, vec)) {
-        long long nb;
-        if (int rc = tvm::D_admm_zu(g, d, x, x_prev, x_next, st, &nb, (float*)z, (float*)u, (float)thresh, P.slot(0), tform)) return rc;
-        return P.reduce(0, nb, tvout, st);
-    }
-    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
-        LC lc = launch_cfg(d, V, d.nz);
-        AdmmZU<S, T, V> epi{(T*)z, (T*)u, (T)thresh, P.slot(0), tform};
-        hipLaunchKernelGGL((k_D<S, T, V, AdmmZU<S, T, V>>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x,
-                           (const T*)x_prev, (const T*)x_next, 1, 0, epi);
-        HIP_TRY(hipGetLastError());
-        return P.reduce(0, lc.nblocks, tvout, st);
-    });
+    Call c{g, d, x, x_prev, x_next, st};
+    return run_D<AdmmZU>(c, vec, march_ok(g, d, vec), [&]<typename T>() {
+        return AdmmZUArgs<T>{(T*)z, (T*)u, (T)thresh, P.slot(0), tform};
+    }, P, tvout);
 }
 int tv_admm_zu(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* z, void* u,
                double thresh, double* tvout, void* ws, void* stream) {

@@ -3,21 +3,19 @@
 #include "tv_stencil.h"
 #include "tv_march.h"
 
-// NO_WIDE16: leave out M = 16 of the schemes with a 16-frame-wide working set (central, hybrid), where an 8-vector epilogue spills
-// (CpDual: 164 / 340 bytes of scratch per lane); the caller keeps those geometries on the one-site kernel (tvm::D_cp_dual_huber_ok)
-template <template <int, typename, int> class EpiT, bool NO_WIDE16 = false, typename... Args>
-static int launch_D_march(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st,
-                          long long* nblocks, Args... args) {
-    const int zc = march_zchunk(d);
-    const LC lc = march_cfg(d, zc);
-    *nblocks = lc.nblocks;
-    return dispatch_scheme_m(MarchMs{}, g->scheme, d.m, kNoMarchSM, [&]<int S, int M>() -> int {
-        if constexpr (NO_WIDE16 && M == 16 && (S == CENTRAL || S == HYBRID)) {
+// NO_WIDE16: leave out the (scheme, M) of wide16() (tv_host.h); the caller keeps those geometries on the one-site kernel
+template <template <int, typename, int> class EpiT, bool NO_WIDE16 = false, typename Args>
+static int launch_D_march(Call& c, const Args& args) {
+    const int zc = march_zchunk(c.d);
+    const LC lc = march_cfg(c.d, zc);
+    c.nblocks = lc.nblocks;
+    return dispatch_scheme_m(MarchMs{}, c.g->scheme, c.d.m, kNoMarchSM, [&]<int S, int M>() -> int {
+        if constexpr (NO_WIDE16 && wide16(S, M)) {
             return fail(TV_E_ARG, kNoMarchSM);
         } else {
-            EpiT<S, float, 4> epi{args...};
-            hipLaunchKernelGGL((k_D_march<S, M, EpiT<S, float, 4>>), lc.grid, lc.block, 0, st, d, make_w<float>(g), (const float*)x,
-                               (const float*)xp, (const float*)xn, zc, epi);
+            EpiT<S, float, 4> epi{args};
+            hipLaunchKernelGGL((k_D_march<S, M, EpiT<S, float, 4>>), lc.grid, lc.block, 0, c.st, c.d, make_w<float>(c.g), (const float*)c.c,
+                               (const float*)c.prev, (const float*)c.next, zc, epi);
             HIP_TRY(hipGetLastError());
             return 0;
         }
@@ -25,26 +23,11 @@ static int launch_D_march(const tv_geom* g, const DG& d, const void* x, const vo
 }
 
 namespace tvm {
-int D_store(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb, float* dout) {
-    return launch_D_march<StoreD>(g, d, x, xp, xn, st, nb, dout, (double*)nullptr);
-}
-int D_cp_dual(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-              float* q, float sigma, float inv_lambda, double* partials) {
-    return launch_D_march<CpDual>(g, d, x, xp, xn, st, nb, q, sigma, inv_lambda, partials);
-}
-int D_cp_dual_huber(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-                    float* q, float sigma, float shrink, float inv_lambda, double alpha, double half_inv_alpha, double* partials) {
-    return launch_D_march<CpDualHuber, true>(g, d, x, xp, xn, st, nb, q, sigma, shrink, inv_lambda, alpha, half_inv_alpha, partials);
-}
-bool D_cp_dual_huber_ok(const tv_geom* g, const DG& d) { return !(d.m == 16 && (g->scheme == TV_CENTRAL || g->scheme == TV_HYBRID)); }
-int D_admm_zu(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-              float* z, float* u, float thresh, double* partials, int tform) {
-    return launch_D_march<AdmmZU>(g, d, x, xp, xn, st, nb, z, u, thresh, partials, tform);
-}
-int D_gap(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
-          const float* q, const float* x0, float qscale, double lambda, double* p_tv, double* p_fid, double* p_gap) {
-    return launch_D_march<GapD>(g, d, x, xp, xn, st, nb, q, x0, qscale, lambda, p_tv, p_fid, p_gap);
-}
+int D_march(Call& c, const StoreDArgs<float>& a) { return launch_D_march<StoreD>(c, a); }
+int D_march(Call& c, const CpDualArgs<float>& a) { return launch_D_march<CpDual>(c, a); }
+int D_march(Call& c, const CpDualHuberArgs<float>& a) { return launch_D_march<CpDualHuber, true>(c, a); }
+int D_march(Call& c, const AdmmZUArgs<float>& a) { return launch_D_march<AdmmZU>(c, a); }
+int D_march(Call& c, const GapDArgs<float>& a) { return launch_D_march<GapD>(c, a); }
 int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,
             float* norms_ext, double* partials, int ghost_lo, int ghost_hi) {
     const int zc = march_zchunk(d);

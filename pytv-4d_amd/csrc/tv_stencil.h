@@ -193,13 +193,15 @@ template <typename T, int V> __device__ __forceinline__ Vec<T, V> sumsq_slots(co
 
 // =============================================================================================
 // epilogues of the forward kernel
+// An epilogue that is launched from both kernel forms (one site per thread: k_D / k_DT; plane-marching: k_D_march / k_DT_march) keeps its
+// data members in a plain struct XArgs<T> and derives from it: the host names the fields ONCE, where it builds that struct (the entry point
+// in tv_kernels.hip), and both launchers take it whole (run_D / run_DT there, tvm::D_march / tvm::DT_march in tv_march_D/DT.hip).
 // =============================================================================================
-template <int S, typename T, int V> struct StoreD {
+template <typename T> struct StoreDArgs { T* d; double* partials; };
+template <int S, typename T, int V> struct StoreD : StoreDArgs<T> {
     static constexpr bool REDUCES = false;
-    T* d;
-    double* partials;
     __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
-        T* base = d + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        T* base = this->d + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
         for_each_channel<S>(g, [&](auto slot, int ch) { vstore<T, V>(base + (long long)ch * g.s_z, o[decltype(slot)::value]); });
         return 0.0;
     }
@@ -254,16 +256,14 @@ __device__ __forceinline__ double cp_dual_site(const DG& g, const T* base, const
     }
     return acc;
 }
-template <int S, typename T, int V> struct CpDual {
+template <typename T> struct CpDualArgs { T* q; T sigma, inv_lambda; double* partials; };
+template <int S, typename T, int V> struct CpDual : CpDualArgs<T> {
     static constexpr bool REDUCES = true;
-    T* q;
-    T sigma, inv_lambda;
-    double* partials;
     __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
-        T* base = q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        T* base = this->q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
         Vec<T, V> v[8];
         Vec<T, V> scale;
-        const double acc = cp_dual_site<S, T, V>(g, base, o, sigma, inv_lambda, v, scale);
+        const double acc = cp_dual_site<S, T, V>(g, base, o, this->sigma, this->inv_lambda, v, scale);
         for_each_channel<S>(g, [&](auto slot, int ch) {
             constexpr int k = decltype(slot)::value;
             vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);
@@ -298,17 +298,15 @@ __device__ __forceinline__ double cp_dual_huber_site(const DG& g, const T* base,
     }
     return acc;
 }
-template <int S, typename T, int V> struct CpDualHuber {
+template <typename T> struct CpDualHuberArgs { T* q; T sigma, shrink, inv_lambda; double alpha, half_inv_alpha; double* partials; };
+template <int S, typename T, int V> struct CpDualHuber : CpDualHuberArgs<T> {
     static constexpr bool REDUCES = true;
-    T* q;
-    T sigma, shrink, inv_lambda;
-    double alpha, half_inv_alpha;
-    double* partials;
     __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
-        T* base = q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        T* base = this->q + (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
         Vec<T, V> v[8];
         Vec<T, V> scale;
-        const double acc = cp_dual_huber_site<S, T, V>(g, base, o, sigma, shrink, inv_lambda, alpha, half_inv_alpha, v, scale);
+        const double acc = cp_dual_huber_site<S, T, V>(g, base, o, this->sigma, this->shrink, this->inv_lambda, this->alpha,
+                                                       this->half_inv_alpha, v, scale);
         for_each_channel<S>(g, [&](auto slot, int ch) {
             constexpr int k = decltype(slot)::value;
             vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);
@@ -319,20 +317,16 @@ template <int S, typename T, int V> struct CpDualHuber {
 
 // ADMM: v = Dx + u;  z = v * max(0, 1 - thresh/|v|);  u = v - z.   tform: the first array receives t = z - u_new
 // (= 2 z - v) instead of z: the next right-hand side x0 + rho D^T (z - u) then reads ONE gradient array
-template <int S, typename T, int V> struct AdmmZU {
+template <typename T> struct AdmmZUArgs { T* z; T* u; T thresh; double* partials; int tform = 0; };
+template <int S, typename T, int V> struct AdmmZU : AdmmZUArgs<T> {
     static constexpr bool REDUCES = true;
-    T* z;
-    T* u;
-    T thresh;
-    double* partials;
-    int tform = 0;
     __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
         const long long off = (long long)c.zl * g.s_dz + (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
         Vec<T, V> v[8];
         Vec<T, V> vs = vsplat<T, V>(T(0));
         for_each_channel<S>(g, [&](auto slot, int ch) {
             constexpr int k = decltype(slot)::value;
-            v[k] = o[k] + vload<T, V>(u + off + (long long)ch * g.s_z);
+            v[k] = o[k] + vload<T, V>(this->u + off + (long long)ch * g.s_z);
             vs = vs + v[k] * v[k];
         });
         const Vec<T, V> ds = sumsq_slots<T, V>(o);
@@ -342,14 +336,14 @@ template <int S, typename T, int V> struct AdmmZU {
         for (int i = 0; i < V; ++i) {
             acc += (double)tsqrt(ds.v[i]);
             const T nv = tsqrt(vs.v[i]);
-            scale.v[i] = (nv > T(0)) ? tmax(T(0), T(1) - thresh / nv) : T(0);
+            scale.v[i] = (nv > T(0)) ? tmax(T(0), T(1) - this->thresh / nv) : T(0);
         }
         for_each_channel<S>(g, [&](auto slot, int ch) {
             constexpr int k = decltype(slot)::value;
             const Vec<T, V> zz = v[k] * scale;
             const Vec<T, V> un = v[k] - zz;
-            vstore<T, V>(z + off + (long long)ch * g.s_z, tform ? zz - un : zz);
-            vstore<T, V>(u + off + (long long)ch * g.s_z, un);
+            vstore<T, V>(this->z + off + (long long)ch * g.s_z, this->tform ? zz - un : zz);
+            vstore<T, V>(this->u + off + (long long)ch * g.s_z, un);
         });
         return acc;
     }
@@ -468,51 +462,48 @@ template <typename T, int V> struct SrcDiff {    // a - b, halos already differe
     __device__ __forceinline__ Vec<T, V> ldn(long long off) const { return vload<T, V>(yn + off); }
 };
 
-template <typename T, int V> struct StoreDT {
+template <typename T> struct StoreDTArgs { T* out; double* partials; };
+template <typename T, int V> struct StoreDT : StoreDTArgs<T> {
     static constexpr bool REDUCES = false;
-    T* out;
-    double* partials;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        vstore<T, V>(out + off, r);
+        vstore<T, V>(this->out + off, r);
         return 0.0;
     }
 };
-template <typename T, int V> struct AxpyDT {     // out = base + beta * base2 + alpha * r
-    static constexpr bool REDUCES = false;
+template <typename T> struct AxpyDTArgs {
     T* out;
     const T* base;
     T alpha;
     double* partials;
     const T* base2 = nullptr;       // tv_DT_axpy2: the primal step of Chambolle-Pock with a data-fidelity operator,
     T beta = T(0);                  // x - tau A^T p - tau D^T q in one pass (base = x, base2 = A^T p, beta = alpha = -tau)
+};
+template <typename T, int V> struct AxpyDT : AxpyDTArgs<T> {     // out = base + beta * base2 + alpha * r
+    static constexpr bool REDUCES = false;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        Vec<T, V> b = (base != nullptr) ? vload_s<T, V>(base + off) : vsplat<T, V>(T(0));
-        if (base2 != nullptr) b = b + beta * vload_s<T, V>(base2 + off);
-        vstore_s<T, V>(out + off, b + alpha * r);
+        Vec<T, V> b = (this->base != nullptr) ? vload_s<T, V>(this->base + off) : vsplat<T, V>(T(0));
+        if (this->base2 != nullptr) b = b + this->beta * vload_s<T, V>(this->base2 + off);
+        vstore_s<T, V>(this->out + off, b + this->alpha * r);
         return 0.0;
     }
 };
 // Chambolle-Pock primal step with the fidelity-dual update folded in, README.md:148,154,157
-template <typename T, int V> struct CpPrimal {
+template <typename T> struct CpPrimalArgs { T* x; const T* x0; T* p; T tau, sigma_a, inv_1p_sigma_a; double* partials; };
+template <typename T, int V> struct CpPrimal : CpPrimalArgs<T> {
     static constexpr bool REDUCES = true;
-    T* x;
-    const T* x0;
-    T* p;
-    T tau, sigma_a, inv_1p_sigma_a;
-    double* partials;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off), pv = vload_s<T, V>(p + off);
+        const Vec<T, V> xv = vload_s<T, V>(this->x + off), x0v = vload_s<T, V>(this->x0 + off), pv = vload_s<T, V>(this->p + off);
         Vec<T, V> pn, xn;
         double acc = 0.0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            pn.v[i] = (pv.v[i] + sigma_a * (xv.v[i] - x0v.v[i])) * inv_1p_sigma_a;
-            xn.v[i] = (xv.v[i] - tau * pn.v[i]) - tau * r.v[i];
+            pn.v[i] = (pv.v[i] + this->sigma_a * (xv.v[i] - x0v.v[i])) * this->inv_1p_sigma_a;
+            xn.v[i] = (xv.v[i] - this->tau * pn.v[i]) - this->tau * r.v[i];
             const double e = (double)xn.v[i] - (double)x0v.v[i];
             acc += 0.5 * e * e;
         }
-        vstore_s<T, V>(p + off, pn);
-        vstore_s<T, V>(x + off, xn);
+        vstore_s<T, V>(this->p + off, pn);
+        vstore_s<T, V>(this->x + off, xn);
         return acc;
     }
 };
@@ -520,26 +511,22 @@ template <typename T, int V> struct CpPrimal {
 // Accelerated Chambolle-Pock primal step (Chambolle & Pock 2011, Algorithm 2, for the 1-strongly convex fidelity 1/2 |x - x0|^2):
 //   x_new = (x - tau D^T q + tau x0) / (1 + tau);  x_bar = x_new + theta (x_new - x);  x = x_new          (tv_cp_primal_accel)
 // inv_1p_tau = 1 / (1 + tau) is formed by the host in double.  x and x_bar are different arrays; pads stay zero (r, x, x0 are zero there).
-template <typename T, int V> struct CpPrimalAccel {
+template <typename T> struct CpPrimalAccelArgs { T* x; T* x_bar; const T* x0; T tau, inv_1p_tau, theta; double* partials; };
+template <typename T, int V> struct CpPrimalAccel : CpPrimalAccelArgs<T> {
     static constexpr bool REDUCES = true;
-    T* x;
-    T* x_bar;
-    const T* x0;
-    T tau, inv_1p_tau, theta;
-    double* partials;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        const Vec<T, V> xv = vload_s<T, V>(this->x + off), x0v = vload_s<T, V>(this->x0 + off);
         Vec<T, V> xn, xb;
         double acc = 0.0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            xn.v[i] = ((xv.v[i] - tau * r.v[i]) + tau * x0v.v[i]) * inv_1p_tau;
-            xb.v[i] = xn.v[i] + theta * (xn.v[i] - xv.v[i]);
+            xn.v[i] = ((xv.v[i] - this->tau * r.v[i]) + this->tau * x0v.v[i]) * this->inv_1p_tau;
+            xb.v[i] = xn.v[i] + this->theta * (xn.v[i] - xv.v[i]);
             const double e = (double)xn.v[i] - (double)x0v.v[i];
             acc += 0.5 * e * e;
         }
-        vstore_s<T, V>(x + off, xn);
-        vstore_s<T, V>(x_bar + off, xb);
+        vstore_s<T, V>(this->x + off, xn);
+        vstore_s<T, V>(this->x_bar + off, xb);
         return acc;
     }
 };
@@ -556,40 +543,35 @@ template <typename T, int V> struct CpPrimalAccel {
 // L2: cap = +inf, half_inv = 1/2).  Pads stay zero (r, x, x0 are zero there: e = 0, prox(0) = 0).
 __device__ __forceinline__ float  tclamp(float v, float t)   { return __builtin_amdgcn_fmed3f(v, -t, t); }
 __device__ __forceinline__ double tclamp(double v, double t) { return fmin(fmax(v, -t), t); }
-template <typename T, int V, bool STORE> struct CpPrimalProxT {
+template <typename T> struct CpPrimalProxArgs { T* x; T* x_bar; const T* x0; T tau, theta, c, t; double cap, half_inv, inv_tau; double* partials; };
+template <typename T, int V, bool STORE> struct CpPrimalProxT : CpPrimalProxArgs<T> {
     static constexpr bool REDUCES = true;
-    T* x;
-    T* x_bar;
-    const T* x0;
-    T tau, theta, c, t;
-    double cap, half_inv, inv_tau;
-    double* partials;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        const Vec<T, V> xv = vload_s<T, V>(this->x + off), x0v = vload_s<T, V>(this->x0 + off);
         Vec<T, V> xn, xb;
         double acc = 0.0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const T e = (xv.v[i] - tau * r.v[i]) - x0v.v[i];
-            xn.v[i] = x0v.v[i] + (e - tclamp(c * e, t));
+            const T e = (xv.v[i] - this->tau * r.v[i]) - x0v.v[i];
+            xn.v[i] = x0v.v[i] + (e - tclamp(this->c * e, this->t));
             if (STORE) {
-                xb.v[i] = xn.v[i] + theta * (xn.v[i] - xv.v[i]);
+                xb.v[i] = xn.v[i] + this->theta * (xn.v[i] - xv.v[i]);
                 const double ae = fabs((double)xn.v[i] - (double)x0v.v[i]);
-                const double a = fmin(ae, cap);
-                acc += (ae - a) + a * a * half_inv;
+                const double a = fmin(ae, this->cap);
+                acc += (ae - a) + a * a * this->half_inv;
             } else {
-                const double d = ((double)xv.v[i] - (double)xn.v[i]) * inv_tau;
+                const double d = ((double)xv.v[i] - (double)xn.v[i]) * this->inv_tau;
                 acc += d * d;
             }
         }
         if (STORE) {
-            vstore_s<T, V>(x + off, xn);
-            vstore_s<T, V>(x_bar + off, xb);
+            vstore_s<T, V>(this->x + off, xn);
+            vstore_s<T, V>(this->x_bar + off, xb);
         }
         return acc;
     }
 };
-template <typename T, int V> using CpPrimalProx = CpPrimalProxT<T, V, true>;       // the <typename, int> forms launch_DT_march takes
+template <typename T, int V> using CpPrimalProx = CpPrimalProxT<T, V, true>;       // the <typename, int> forms the launchers take: pick_store
 template <typename T, int V> using CpPrimalProxRes = CpPrimalProxT<T, V, false>;
 
 // Chambolle-Pock primal step for the POISSON data term, the generalised Kullback-Leibler divergence F(x) = sum (x - x0 + x0 log(x0 / x)) over
@@ -610,26 +592,21 @@ template <typename T> __device__ __forceinline__ double kl_term(T xn, T x0) {
     const T u = (xn - x0) / x0;
     return (double)(x0 > T(0) ? x0 * (u - tlog1p(u)) : xn);
 }
-template <typename T, int V, bool STORE> struct CpPrimalKLT {
+template <typename T> struct CpPrimalKLArgs { T* x; T* x_bar; const T* x0; T tau, theta, two_tau, four_tau; double inv_tau; double* partials; };
+template <typename T, int V, bool STORE> struct CpPrimalKLT : CpPrimalKLArgs<T> {
     static constexpr bool REDUCES = true;
-    T* x;
-    T* x_bar;
-    const T* x0;
-    T tau, theta, two_tau, four_tau;
-    double inv_tau;
-    double* partials;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        const Vec<T, V> xv = vload_s<T, V>(this->x + off), x0v = vload_s<T, V>(this->x0 + off);
         Vec<T, V> xn, xb;
         double acc = 0.0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const T b = (xv.v[i] - tau * r.v[i]) - tau;
-            const T s = tsqrt(tfma(b, b, four_tau * x0v.v[i]));
-            const T hi = T(0.5) * (b + s), lo = (two_tau * x0v.v[i]) / (s - b);
+            const T b = (xv.v[i] - this->tau * r.v[i]) - this->tau;
+            const T s = tsqrt(tfma(b, b, this->four_tau * x0v.v[i]));
+            const T hi = T(0.5) * (b + s), lo = (this->two_tau * x0v.v[i]) / (s - b);
             xn.v[i] = b >= T(0) ? hi : lo;
             if (STORE) {
-                xb.v[i] = xn.v[i] + theta * (xn.v[i] - xv.v[i]);
+                xb.v[i] = xn.v[i] + this->theta * (xn.v[i] - xv.v[i]);
                 acc += kl_term(xn.v[i], x0v.v[i]);
             } else {
                 // x_new - x = (s - c) / 2 with c = 2 x - b = x + tau (1 + r), and s^2 - c^2 = 4 tau (x0 - x (1 + r)): for c >= 0 the
@@ -637,16 +614,16 @@ template <typename T, int V, bool STORE> struct CpPrimalKLT {
                 // The numerator is rounded in T: near a fixed point that is not exactly one it cancels, and (x_new - x) / tau carries
                 // about 2 eps (x0 + |x| |1 + r|) / (s + c) per site -- bounded by the eps |x| / tau that x - x_new carries, so the sum
                 // equals sum ((x - x_new) / tau)^2 to rounding, not bit for bit.
-                const T c = (xv.v[i] + tau * r.v[i]) + tau;
+                const T c = (xv.v[i] + this->tau * r.v[i]) + this->tau;
                 const double den = (double)s + (double)c;
                 const double moved = 2.0 * (double)(x0v.v[i] - xv.v[i] * (T(1) + r.v[i])) / den;
-                const double d = (c >= T(0) && den > 0.0) ? moved : ((double)xn.v[i] - (double)xv.v[i]) * inv_tau;
+                const double d = (c >= T(0) && den > 0.0) ? moved : ((double)xn.v[i] - (double)xv.v[i]) * this->inv_tau;
                 acc += d * d;
             }
         }
         if (STORE) {
-            vstore_s<T, V>(x + off, xn);
-            vstore_s<T, V>(x_bar + off, xb);
+            vstore_s<T, V>(this->x + off, xn);
+            vstore_s<T, V>(this->x_bar + off, xb);
         }
         return acc;
     }
@@ -728,8 +705,7 @@ __device__ __forceinline__ void gap_terms_huber(const Vec<T, V> (&o)[8], const V
 }
 // D-side pass of the plane-marching form (k_D_march): |D x|_{2,1}, 1/2 |x - x0|^2 and sum (lambda |D x|_2 - <qs, D x>); reads x0 and q once.
 // The D^T-side pass (GapDT) ran BEFORE it on the same grid and left its per-block sums in `partials`: finish() adds to them.
-template <int S, typename T, int V> struct GapD {
-    static constexpr bool REDUCES = false;       // three sums, written by finish()
+template <typename T> struct GapDArgs {
     const T* q;
     const T* x0;
     T qscale;
@@ -737,44 +713,44 @@ template <int S, typename T, int V> struct GapD {
     double* p_tv;
     double* p_fid;
     double* partials;     // the gap sums (the name k_D_march expects of an epilogue)
+};
+template <int S, typename T, int V> struct GapD : GapDArgs<T> {
+    static constexpr bool REDUCES = false;       // three sums, written by finish()
     double a_tv = 0.0, a_fid = 0.0, a_gap = 0.0;
     __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8], const Vec<T, V>& xc) {
         const long long inpl = (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
-        const T* base = q + (long long)c.zl * g.s_dz + inpl;
+        const T* base = this->q + (long long)c.zl * g.s_dz + inpl;
         Vec<T, V> qv[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) qv[k] = vsplat<T, V>(T(0));
         for_each_channel<S>(g, [&](auto slot, int ch) {
-            qv[decltype(slot)::value] = qscale * vload_s<T, V>(base + (long long)ch * g.s_z);
+            qv[decltype(slot)::value] = this->qscale * vload_s<T, V>(base + (long long)ch * g.s_z);
         });
-        const Vec<T, V> x0v = vload_s<T, V>(x0 + (long long)c.zl * g.s_z + inpl);
-        gap_terms<T, V>(o, qv, xc, x0v, nullptr, lambda, a_tv, a_fid, a_gap);
+        const Vec<T, V> x0v = vload_s<T, V>(this->x0 + (long long)c.zl * g.s_z + inpl);
+        gap_terms<T, V>(o, qv, xc, x0v, nullptr, this->lambda, a_tv, a_fid, a_gap);
         return 0.0;
     }
     __device__ __forceinline__ void finish(double* sm) {
         const long long b = linear_block_id();
         const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
         const double tv = block_sum(a_tv, sm);
-        if (first) p_tv[b] = tv;
+        if (first) this->p_tv[b] = tv;
         const double fid = block_sum(a_fid, sm);
-        if (first) p_fid[b] = fid;
+        if (first) this->p_fid[b] = fid;
         const double gap = block_sum(a_gap, sm);
-        if (first) partials[b] = partials[b] + gap;
+        if (first) this->partials[b] = this->partials[b] + gap;
     }
 };
 // D^T-side pass of the plane-marching form (k_DT_march): sum 1/2 (x - x0 + qscale D^T q)^2; reads x and x0 once
-template <typename T, int V> struct GapDT {
+template <typename T> struct GapDTArgs { const T* x; const T* x0; T qscale; double* partials; };
+template <typename T, int V> struct GapDT : GapDTArgs<T> {
     static constexpr bool REDUCES = true;
-    const T* x;
-    const T* x0;
-    T qscale;
-    double* partials;
     __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
-        const Vec<T, V> xv = vload_s<T, V>(x + off), x0v = vload_s<T, V>(x0 + off);
+        const Vec<T, V> xv = vload_s<T, V>(this->x + off), x0v = vload_s<T, V>(this->x0 + off);
         double acc = 0.0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const double e = ((double)xv.v[i] - (double)x0v.v[i]) + (double)(qscale * r.v[i]);
+            const double e = ((double)xv.v[i] - (double)x0v.v[i]) + (double)(this->qscale * r.v[i]);
             acc += 0.5 * e * e;
         }
         return acc;

@@ -1,9 +1,11 @@
 """CPU-side pins of the host launch layer (csrc/tv_host.h and the entry points built on it): the size of the reduction workspace, the
-two-plane halo rule of the radius-2 entry points and the FIRST error each one-sweep entry point reports for a bad call.  Every call
+two-plane halo rule of the radius-2 entry points and the FIRST error each one-sweep entry point and each D / D^T epilogue entry point
+reports for a bad call.  Every call
 here returns from an argument check: the pointers (4096 and its multiples) are never followed and nothing is launched.  No GPU.
 
 The literal tables were recorded from the library before the host layer was refactored (commit 9dfb747); they are the behaviour a
-change of that layer has to keep.
+change of that layer has to keep.  EPI_FIRST_ERROR was recorded in the same way before the epilogue launch layer was folded into one pair
+of runners (commit 649149b).
 
 Not covered, on purpose:
   * the three "unsupported (scheme, M) ..." texts of the dispatchers: no entry point can reach them without a launch -- make_dg refuses
@@ -222,3 +224,195 @@ def test_first_error_of_the_one_sweep_entry_points(dtype):
     for key, call in _sweep_calls(lib, bad).items():
         if key[1] == "nx32":
             assert call() == -1 and lib.tv_last_error().decode().startswith("tv_geom was built against another version"), key
+
+
+# ---- first error of the D / D^T epilogue entry points ---------------------------------------------------------------------------------
+# Ordered parameters after the geometry (the stream, always NULL, comes last): pointers default to distinct non-NULL values, the halo
+# planes to NULL.  Every call below is made on an INTERIOR slab (3 x 1 x 8 x 8 at z0 = 3 of 9 planes, with a z term) whose halo planes are
+# missing unless the case says otherwise, so a call that passes every argument check still returns from the halo check -- the last check
+# before the launch -- and never touches the device.  That also pins the order "arguments before halos", and which scalars an entry point
+# does NOT check (tv_cp_dual takes lambda = +inf, nobody looks at sigma_D, sigma_A or thresh).
+HUBER_FID, RESIDUAL = 2, 1
+_X = [("c", P), ("prev", None), ("next", None)]                  # the centre array of the stencil and its halo planes
+EPI_PARAMS = {
+    "tv_cp_dual": _X + [("q", P2), ("sigma_D", 0.3), ("lambda", 5.0), ("out", P3), ("ws", P4)],
+    "tv_cp_dual_huber": _X + [("q", P2), ("sigma_D", 0.3), ("lambda", 5.0), ("alpha", 0.1), ("out", P3), ("ws", P4)],
+    "tv_admm_zu": _X + [("z", P2), ("u", P3), ("thresh", 0.1), ("out", P4), ("ws", P5)],
+    "tv_admm_tu": _X + [("z", P2), ("u", P3), ("thresh", 0.1), ("out", P4), ("ws", P5)],
+    "tv_cp_primal": _X + [("x", P2), ("x0", P3), ("p", P4), ("tau", 0.3), ("sigma_A", 1.0), ("out", P5), ("ws", P6)],
+    "tv_cp_primal_accel": _X + [("x", P2), ("x_bar", P3), ("x0", P4), ("tau", 0.3), ("theta", 0.5), ("out", P5), ("ws", P6)],
+    "tv_cp_primal_prox": _X + [("x", P2), ("x_bar", P3), ("x0", P4), ("fidelity", HUBER_FID), ("delta", 0.5), ("tau", 0.3), ("theta", 0.5),
+                               ("flags", 0), ("out", P5), ("ws", P6)],
+    "tv_cp_primal_kl": _X + [("x", P2), ("x_bar", P3), ("x0", P4), ("tau", 0.3), ("theta", 0.5), ("flags", 0), ("out", P5), ("ws", P6)],
+}
+# (entry point, flags): the prox and KL entries in step mode and in residual mode
+EPI_ENTRIES = [(n, None) for n in EPI_PARAMS if "flags" not in dict(EPI_PARAMS[n])] + [(n, f) for n in ("tv_cp_primal_prox", "tv_cp_primal_kl")
+                                                                                        for f in (0, RESIDUAL)]
+BAD_SCALARS = (("0", 0.0), ("neg", -1.0), ("nan", float("nan")), ("+inf", float("inf")), ("-inf", float("-inf")))
+ALL_SCHEMES = ("upwind", "downwind", "central", "hybrid")
+
+
+def _halo_needed(name, scheme, side):
+    """check_x_halos / check_y_halos: the forward stencil of `upwind` looks at the next plane only, its adjoint at the previous one only"""
+    forward = name in ("tv_cp_dual", "tv_cp_dual_huber", "tv_admm_zu", "tv_admm_tu")
+    return scheme != {(True, "prev"): "upwind", (True, "next"): "downwind", (False, "prev"): "downwind", (False, "next"): "upwind"}[(forward, side)]
+
+
+def _epi_cases(name, flags):
+    """case -> (scheme, overrides).  Every case holds at least one fault that the entry point reports: none of them launches."""
+    params = dict(EPI_PARAMS[name])
+    arrays = [k for k, v in EPI_PARAMS[name] if isinstance(v, int) and k not in ("fidelity", "flags")]
+    scalars = [k for k, v in EPI_PARAMS[name] if isinstance(v, float)]
+    cases = {}
+    for a in arrays:
+        cases["null:" + a] = ("hybrid", {a: None})
+    for s in scalars:
+        for tag, v in BAD_SCALARS:
+            cases["%s=%s" % (s, tag)] = ("hybrid", {s: v})
+    if "x_bar" in params:
+        cases["x==x_bar"] = ("hybrid", {"x_bar": params["x"]})
+    if "flags" in params:
+        cases["flags=2"], cases["flags=4|mode"] = ("hybrid", {"flags": 2}), ("hybrid", {"flags": 4 | flags})
+        cases["flag+null"] = ("hybrid", {"flags": 2, "c": None})              # two faults: the flag comes before the NULL
+    if "fidelity" in params:
+        cases["fidelity=-1"], cases["fidelity=3"] = ("hybrid", {"fidelity": -1}), ("hybrid", {"fidelity": 3})
+        cases["fidelity+flag"] = ("hybrid", {"fidelity": 3, "flags": 2})
+    for s in scalars:
+        cases["null+%s" % s] = ("hybrid", {"c": None, s: -1.0})               # two faults: the NULL comes before the scalar
+    if "x_bar" in params:
+        cases["alias+tau"] = ("hybrid", {"x_bar": params["x"], "tau": -1.0})
+    # halos (every scalar case above is "scalar + missing halo" already): one side missing where the scheme needs that side -- where it does
+    # not, the call would pass -- and both missing, for every scheme
+    for scheme in ALL_SCHEMES:
+        for side, other in (("prev", "next"), ("next", "prev")):
+            if _halo_needed(name, scheme, side):
+                cases["halo:%s:%s" % (scheme, side)] = (scheme, {other: P6})
+        cases["halo:%s:both" % scheme] = (scheme, {})
+    return cases
+
+
+def _epi_call(nv, lib, name, flags, scheme, dtype, overrides):
+    g = _geom(nv, nz=3, m=1, ny=8, nx=8, nz_global=9, z0=3, scheme=scheme, dtype=dtype, rz=1.0, rt=0.0)
+    a = dict(EPI_PARAMS[name])
+    if flags is not None:
+        a["flags"] = flags
+    a.update(overrides)
+    assert set(a) == set(dict(EPI_PARAMS[name]))
+    rc = getattr(lib, name)(ctypes.byref(g), *[a[k] for k, _ in EPI_PARAMS[name]], None)
+    return rc, lib.tv_last_error().decode()
+
+
+# the texts, by the short names the table below uses; the return code is -2 for the two halo texts and -1 for everything else
+EPI_TEXT = {
+    "NULL": "NULL array",
+    "prev_x": "previous-slab halo plane required", "next_x": "next-slab halo plane required",
+    "prev_y": "previous-slab gradient halo required", "next_y": "next-slab gradient halo required",
+    "lambda": "lambda must be > 0", "lambda_f": "lambda must be a finite number > 0",
+    "alpha": "alpha must be a finite number > 0 (alpha = 0 is plain TV: tv_cp_dual)",
+    "sigma_D": "sigma_D must be a finite number > 0",
+    "alias": "x and x_bar must be different arrays",
+    "tau": "tau must be a finite number > 0", "theta": "theta must be a finite number in [0, 1]", "delta": "delta must be a finite number > 0",
+    "fid": "unknown fidelity", "flag": "unknown flag bits",
+}
+EPI_HALO_TEXTS = ("prev_x", "next_x", "prev_y", "next_y")
+# (entry point, flags) -> case -> text; recorded, the same for fp32 and fp64
+EPI_FIRST_ERROR = {
+    ("tv_cp_dual", None): {
+        "null:c": "NULL", "null:q": "NULL", "null:out": "NULL", "null:ws": "NULL", "sigma_D=0": "prev_x", "sigma_D=neg": "prev_x",
+        "sigma_D=nan": "prev_x", "sigma_D=+inf": "prev_x", "sigma_D=-inf": "prev_x", "lambda=0": "lambda", "lambda=neg": "lambda",
+        "lambda=nan": "lambda", "lambda=+inf": "prev_x", "lambda=-inf": "lambda", "null+sigma_D": "NULL", "null+lambda": "NULL",
+        "halo:upwind:next": "next_x", "halo:upwind:both": "next_x", "halo:downwind:prev": "prev_x", "halo:downwind:both": "prev_x",
+        "halo:central:prev": "prev_x", "halo:central:next": "next_x", "halo:central:both": "prev_x", "halo:hybrid:prev": "prev_x",
+        "halo:hybrid:next": "next_x", "halo:hybrid:both": "prev_x",
+    },
+    ("tv_cp_dual_huber", None): {
+        "null:c": "NULL", "null:q": "NULL", "null:out": "NULL", "null:ws": "NULL", "sigma_D=0": "sigma_D", "sigma_D=neg": "sigma_D",
+        "sigma_D=nan": "sigma_D", "sigma_D=+inf": "sigma_D", "sigma_D=-inf": "sigma_D", "lambda=0": "lambda_f", "lambda=neg": "lambda_f",
+        "lambda=nan": "lambda_f", "lambda=+inf": "lambda_f", "lambda=-inf": "lambda_f", "alpha=0": "alpha", "alpha=neg": "alpha",
+        "alpha=nan": "alpha", "alpha=+inf": "alpha", "alpha=-inf": "alpha", "null+sigma_D": "NULL", "null+lambda": "NULL",
+        "null+alpha": "NULL", "halo:upwind:next": "next_x", "halo:upwind:both": "next_x", "halo:downwind:prev": "prev_x",
+        "halo:downwind:both": "prev_x", "halo:central:prev": "prev_x", "halo:central:next": "next_x", "halo:central:both": "prev_x",
+        "halo:hybrid:prev": "prev_x", "halo:hybrid:next": "next_x", "halo:hybrid:both": "prev_x",
+    },
+    ("tv_admm_zu", None): {
+        "null:c": "NULL", "null:z": "NULL", "null:u": "NULL", "null:out": "NULL", "null:ws": "NULL", "thresh=0": "prev_x",
+        "thresh=neg": "prev_x", "thresh=nan": "prev_x", "thresh=+inf": "prev_x", "thresh=-inf": "prev_x", "null+thresh": "NULL",
+        "halo:upwind:next": "next_x", "halo:upwind:both": "next_x", "halo:downwind:prev": "prev_x", "halo:downwind:both": "prev_x",
+        "halo:central:prev": "prev_x", "halo:central:next": "next_x", "halo:central:both": "prev_x", "halo:hybrid:prev": "prev_x",
+        "halo:hybrid:next": "next_x", "halo:hybrid:both": "prev_x",
+    },
+    ("tv_admm_tu", None): {
+        "null:c": "NULL", "null:z": "NULL", "null:u": "NULL", "null:out": "NULL", "null:ws": "NULL", "thresh=0": "prev_x",
+        "thresh=neg": "prev_x", "thresh=nan": "prev_x", "thresh=+inf": "prev_x", "thresh=-inf": "prev_x", "null+thresh": "NULL",
+        "halo:upwind:next": "next_x", "halo:upwind:both": "next_x", "halo:downwind:prev": "prev_x", "halo:downwind:both": "prev_x",
+        "halo:central:prev": "prev_x", "halo:central:next": "next_x", "halo:central:both": "prev_x", "halo:hybrid:prev": "prev_x",
+        "halo:hybrid:next": "next_x", "halo:hybrid:both": "prev_x",
+    },
+    ("tv_cp_primal", None): {
+        "null:c": "NULL", "null:x": "NULL", "null:x0": "NULL", "null:p": "NULL", "null:out": "NULL", "null:ws": "NULL", "tau=0": "prev_y",
+        "tau=neg": "prev_y", "tau=nan": "prev_y", "tau=+inf": "prev_y", "tau=-inf": "prev_y", "sigma_A=0": "prev_y",
+        "sigma_A=neg": "prev_y", "sigma_A=nan": "prev_y", "sigma_A=+inf": "prev_y", "sigma_A=-inf": "prev_y", "null+tau": "NULL",
+        "null+sigma_A": "NULL", "halo:upwind:prev": "prev_y", "halo:upwind:both": "prev_y", "halo:downwind:next": "next_y",
+        "halo:downwind:both": "next_y", "halo:central:prev": "prev_y", "halo:central:next": "next_y", "halo:central:both": "prev_y",
+        "halo:hybrid:prev": "prev_y", "halo:hybrid:next": "next_y", "halo:hybrid:both": "prev_y",
+    },
+    ("tv_cp_primal_accel", None): {
+        "null:c": "NULL", "null:x": "NULL", "null:x_bar": "NULL", "null:x0": "NULL", "null:out": "NULL", "null:ws": "NULL", "tau=0": "tau",
+        "tau=neg": "tau", "tau=nan": "tau", "tau=+inf": "tau", "tau=-inf": "tau", "theta=0": "prev_y", "theta=neg": "theta",
+        "theta=nan": "theta", "theta=+inf": "theta", "theta=-inf": "theta", "x==x_bar": "alias", "null+tau": "NULL", "null+theta": "NULL",
+        "alias+tau": "alias", "halo:upwind:prev": "prev_y", "halo:upwind:both": "prev_y", "halo:downwind:next": "next_y",
+        "halo:downwind:both": "next_y", "halo:central:prev": "prev_y", "halo:central:next": "next_y", "halo:central:both": "prev_y",
+        "halo:hybrid:prev": "prev_y", "halo:hybrid:next": "next_y", "halo:hybrid:both": "prev_y",
+    },
+    ("tv_cp_primal_prox", 0): {
+        "null:c": "NULL", "null:x": "NULL", "null:x_bar": "NULL", "null:x0": "NULL", "null:out": "NULL", "null:ws": "NULL",
+        "delta=0": "delta", "delta=neg": "delta", "delta=nan": "delta", "delta=+inf": "delta", "delta=-inf": "delta", "tau=0": "tau",
+        "tau=neg": "tau", "tau=nan": "tau", "tau=+inf": "tau", "tau=-inf": "tau", "theta=0": "prev_y", "theta=neg": "theta",
+        "theta=nan": "theta", "theta=+inf": "theta", "theta=-inf": "theta", "x==x_bar": "alias", "flags=2": "flag", "flags=4|mode": "flag",
+        "flag+null": "flag", "fidelity=-1": "fid", "fidelity=3": "fid", "fidelity+flag": "fid", "null+delta": "NULL", "null+tau": "NULL",
+        "null+theta": "NULL", "alias+tau": "alias", "halo:upwind:prev": "prev_y", "halo:upwind:both": "prev_y",
+        "halo:downwind:next": "next_y", "halo:downwind:both": "next_y", "halo:central:prev": "prev_y", "halo:central:next": "next_y",
+        "halo:central:both": "prev_y", "halo:hybrid:prev": "prev_y", "halo:hybrid:next": "next_y", "halo:hybrid:both": "prev_y",
+    },
+    ("tv_cp_primal_prox", 1): {
+        "null:c": "NULL", "null:x": "NULL", "null:x_bar": "prev_y", "null:x0": "NULL", "null:out": "NULL", "null:ws": "NULL",
+        "delta=0": "delta", "delta=neg": "delta", "delta=nan": "delta", "delta=+inf": "delta", "delta=-inf": "delta", "tau=0": "tau",
+        "tau=neg": "tau", "tau=nan": "tau", "tau=+inf": "tau", "tau=-inf": "tau", "theta=0": "prev_y", "theta=neg": "prev_y",
+        "theta=nan": "prev_y", "theta=+inf": "prev_y", "theta=-inf": "prev_y", "x==x_bar": "alias", "flags=2": "flag",
+        "flags=4|mode": "flag", "flag+null": "flag", "fidelity=-1": "fid", "fidelity=3": "fid", "fidelity+flag": "fid",
+        "null+delta": "NULL", "null+tau": "NULL", "null+theta": "NULL", "alias+tau": "alias", "halo:upwind:prev": "prev_y",
+        "halo:upwind:both": "prev_y", "halo:downwind:next": "next_y", "halo:downwind:both": "next_y", "halo:central:prev": "prev_y",
+        "halo:central:next": "next_y", "halo:central:both": "prev_y", "halo:hybrid:prev": "prev_y", "halo:hybrid:next": "next_y",
+        "halo:hybrid:both": "prev_y",
+    },
+    ("tv_cp_primal_kl", 0): {
+        "null:c": "NULL", "null:x": "NULL", "null:x_bar": "NULL", "null:x0": "NULL", "null:out": "NULL", "null:ws": "NULL", "tau=0": "tau",
+        "tau=neg": "tau", "tau=nan": "tau", "tau=+inf": "tau", "tau=-inf": "tau", "theta=0": "prev_y", "theta=neg": "theta",
+        "theta=nan": "theta", "theta=+inf": "theta", "theta=-inf": "theta", "x==x_bar": "alias", "flags=2": "flag", "flags=4|mode": "flag",
+        "flag+null": "flag", "null+tau": "NULL", "null+theta": "NULL", "alias+tau": "alias", "halo:upwind:prev": "prev_y",
+        "halo:upwind:both": "prev_y", "halo:downwind:next": "next_y", "halo:downwind:both": "next_y", "halo:central:prev": "prev_y",
+        "halo:central:next": "next_y", "halo:central:both": "prev_y", "halo:hybrid:prev": "prev_y", "halo:hybrid:next": "next_y",
+        "halo:hybrid:both": "prev_y",
+    },
+    ("tv_cp_primal_kl", 1): {
+        "null:c": "NULL", "null:x": "NULL", "null:x_bar": "prev_y", "null:x0": "NULL", "null:out": "NULL", "null:ws": "NULL",
+        "tau=0": "tau", "tau=neg": "tau", "tau=nan": "tau", "tau=+inf": "tau", "tau=-inf": "tau", "theta=0": "prev_y",
+        "theta=neg": "prev_y", "theta=nan": "prev_y", "theta=+inf": "prev_y", "theta=-inf": "prev_y", "x==x_bar": "alias",
+        "flags=2": "flag", "flags=4|mode": "flag", "flag+null": "flag", "null+tau": "NULL", "null+theta": "NULL", "alias+tau": "alias",
+        "halo:upwind:prev": "prev_y", "halo:upwind:both": "prev_y", "halo:downwind:next": "next_y", "halo:downwind:both": "next_y",
+        "halo:central:prev": "prev_y", "halo:central:next": "next_y", "halo:central:both": "prev_y", "halo:hybrid:prev": "prev_y",
+        "halo:hybrid:next": "next_y", "halo:hybrid:both": "prev_y",
+    },
+}
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("name, flags", EPI_ENTRIES)
+def test_first_error_of_the_epilogue_entry_points(name, flags, dtype):
+    nv, lib = _nv()
+    cases, want = _epi_cases(name, flags), EPI_FIRST_ERROR[(name, flags)]
+    assert set(cases) == set(want)
+    for case, (scheme, overrides) in cases.items():
+        rc, text = _epi_call(nv, lib, name, flags, scheme, dtype, overrides)
+        code = want[case]
+        assert (rc, text) == (-2 if code in EPI_HALO_TEXTS else -1, EPI_TEXT[code]), (case, rc, text)

@@ -244,6 +244,33 @@ int tv_cp_primal_prox(const tv_geom* g, const void* q, const void* q_prev, const
 int tv_cp_primal_kl(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar,
                     const void* x0, double tau, double theta, int32_t flags, double* out, void* ws, void* stream);
 
+/* Primal step of Chambolle-Pock (Chambolle & Pock 2011, Algorithm 1) for a WEIGHTED quadratic data term with a BOX constraint,
+ *   F(x) = 1/2 sum_sites w (x - x0)^2  over lo <= x <= hi,  w >= 0 per voxel (an array like x0),
+ * with the extrapolation folded into the same pass.  w = 0 marks a voxel as unknown -- a dead detector module, a masked frame, a metal
+ * trace: TV fills it in (the inpainting model of section 6.3 of the paper); w = 1 / sigma^2 is heteroscedastic least squares.
+ * flags: 0 or TV_CPP_RESIDUAL.
+ * STEP mode (flags == 0), one pass of Nd + 5 words per voxel (tv_cp_primal_prox's Nd + 4 and w):
+ *   v = x - tau D^T q;  c = tau w / (1 + tau w);  x_new = clamp(v - c (v - x0), lo, hi)  -- the prox of a separable term is the clamp of
+ *   the quadratic's prox;  x_bar = x_new + theta (x_new - x);  x = x_new;
+ *   *out (device fp64) = 1/2 sum w (x_new - x0)^2 over the local planes, accumulated in fp64.
+ * Exact by construction: a site with w == 0 returns clamp(v) BIT FOR BIT, a site with v == x0 returns x0 bit for bit (a constant image
+ * inside the box with q = 0 does not move), every x_new lies in [lo, hi].  lo / hi may be -inf / +inf (no bound on that side).
+ * THE BOX MUST CONTAIN 0 (lo <= 0 <= hi, else TV_E_ARG): the pad elements of pitched arrays are computed like voxels -- x, x0, w and
+ * D^T q are 0 there, so they come out as clamp(0) -- and they have to stay 0.  TV and the data term do not change when x, x0 and the box
+ * are shifted by one constant, so a caller with another box shifts the problem (pytv.solvers.WeightedChambollePock does).
+ * The caller's contract: w finite and >= 0 and tau w finite; the kernel does not check it (a negative or infinite w can give NaN).
+ * RESIDUAL mode (flags == TV_CPP_RESIDUAL): REDUCE-ONLY, nothing is written except out and ws; x_bar may be NULL and theta is ignored.
+ *   *out = sum_sites ((x - x_new) / tau)^2 in fp64 -- zero iff -D^T q is in the subdifferential of F at x; with tv_cp_dual_residual an
+ *   optimality certificate of the pair (x, q).  Nd + 3 words per voxel.
+ * q_prev / q_next, geometries and dispatch as tv_cp_primal_kl (four schemes, fp32 / fp64, 16-byte lanes -- w aligned like the others -- or
+ * scalar rows, pitched arrays, mask_static / time_factor / time_weight_vol, z-slabs; fp32 planes of >= 4 MiB take the plane-marching
+ * kernel, both modes); slab partials add up to the unsharded scalars.
+ * TV_E_ARG: an unknown flag bit, a NULL array (x_bar in step mode), x == x_bar, lo or hi NaN, a box that does not contain 0, tau not finite
+ * and > 0, theta not finite or outside [0, 1] (step mode); a missing halo plane is TV_E_HALO; all checks precede any device access. */
+int tv_cp_primal_wls(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar,
+                     const void* x0, const void* w, double lo, double hi, double tau, double theta, int32_t flags,
+                     double* out, void* ws, void* stream);
+
 /* Duality-gap certificate of the model every solver here minimises, P(x) = 1/2 |x - x0|^2 + lambda |D x|_{2,1}, for an iterate x and a dual
  * variable qs = qscale * q with |qs|_2 <= lambda per site (Chambolle-Pock: its q, qscale = 1; scaled-form ADMM: q = u, qscale = rho; both are
  * projections).  Over the local planes, with gd = D^T qs:

@@ -354,6 +354,7 @@ template <typename T> struct StoreDArgs; template <typename T> struct CpDualArgs
 template <typename T> struct AdmmZUArgs; template <typename T> struct GapDArgs; template <typename T> struct StoreDTArgs;
 template <typename T> struct AxpyDTArgs; template <typename T> struct CpPrimalArgs; template <typename T> struct CpPrimalAccelArgs;
 template <typename T> struct CpPrimalProxArgs; template <typename T> struct CpPrimalKLArgs; template <typename T> struct GapDTArgs;
+template <typename T> struct CpPrimalWLSArgs;
 }
 namespace tvm {
 // D x with the epilogue whose arguments are given (fp32): one overload per epilogue, each a line in tv_march_D.hip
@@ -398,5 +399,8 @@ int DT_march(Call& c, const CpPrimalAccelArgs<float>& a);
 int DT_march(Call& c, const CpPrimalProxArgs<float>& a, bool store);
 // primal step for the Poisson / Kullback-Leibler data term (tv_cp_primal_kl; CpPrimalKLT of tv_stencil.h): store / !store as above
 int DT_march(Call& c, const CpPrimalKLArgs<float>& a, bool store);
+// primal step for the weighted quadratic data term with a box (tv_cp_primal_wls; CpPrimalWLST of tv_stencil.h): store = the step (Nd + 5 words
+// per voxel: w is read as well), !store = the reduce-only residual (Nd + 3)
+int DT_march(Call& c, const CpPrimalWLSArgs<float>& a, bool store);
 int DT_march(Call& c, const GapDTArgs<float>& a);             // (see D_march with GapDArgs)
 }  // namespace tvm

@@ -12,6 +12,7 @@
 //                StoreDT / AxpyDT / CpPrimal / CpPrimalAccel epilogues   (tv_DT, tv_DT_axpy, tv_cp_primal, tv_cp_primal_accel)
 //                CpPrimalProxT -> primal step with an L2 / L1 / Huber prox, or its reduce-only residual   (tv_cp_primal_prox)
 //                CpPrimalKLT   -> primal step with the Poisson / Kullback-Leibler prox, or its residual     (tv_cp_primal_kl)
+//                CpPrimalWLST  -> primal step with the weighted least-squares + box prox, or its residual    (tv_cp_primal_wls)
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
 //   k_gap_huber : the same for the Huber-TV regulariser  (tv_dual_gap_huber)
 //   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
@@ -1125,6 +1126,36 @@ int tv_cp_primal_kl(const tv_geom* g, const void* q, const void* q_prev, const v
         return CpPrimalKLArgs<T>{(T*)x, (T*)x_bar, (const T*)x0, (T)tau, (T)th, (T)two_tau, (T)four_tau, inv_tau, P.slot(0)};
     };
     return pick_store<CpPrimalKL, CpPrimalKLRes>(store, [&]<template <typename, int> class E>() {
+        return run_DT<E>(c, vec, march_ok(g, d, vec), args, P, out, store);
+    });
+}
+
+// Chambolle-Pock primal step for the weighted quadratic data term with a box, or its reduce-only fixed-point residual (include/pytv4d.h):
+// tv_cp_primal_kl's checks, gather and launch rules with the CpPrimalWLST epilogue, which reads one more array (w).  The box must contain 0:
+// a pad element is clamp(0) and has to stay 0.
+int tv_cp_primal_wls(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* x_bar, const void* x0,
+                     const void* w, double lo, double hi, double tau, double theta, int32_t flags, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (flags & ~TV_CPP_RESIDUAL) return fail(TV_E_ARG, "unknown flag bits");
+    const bool store = !(flags & TV_CPP_RESIDUAL);
+    if (q == nullptr || x == nullptr || x0 == nullptr || w == nullptr || out == nullptr || ws == nullptr || (store && x_bar == nullptr))
+        return fail(TV_E_ARG, "NULL array");
+    if (x == x_bar) return fail(TV_E_ARG, "x and x_bar must be different arrays");
+    if (std::isnan(lo) || std::isnan(hi)) return fail(TV_E_ARG, "the bounds lo and hi must not be NaN (-inf / +inf: no bound)");
+    if (!(lo <= 0.0 && 0.0 <= hi)) return fail(TV_E_ARG, "the box [lo, hi] must contain 0: pad elements have to stay 0 (shift the problem)");
+    if (!finite_pos(tau)) return fail(TV_E_ARG, "tau must be a finite number > 0");
+    if (store && !finite_in_01(theta)) return fail(TV_E_ARG, "theta must be a finite number in [0, 1]");
+    if (int rc = check_y_halos(g, d, q_prev, q_next)) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({q, q_prev, q_next, x, x_bar, x0, w, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
+    const double th = store ? theta : 0.0, inv_tau = 1.0 / tau;
+    Call c{g, d, q, q_prev, q_next, st};
+    auto args = [&]<typename T>() {
+        return CpPrimalWLSArgs<T>{(T*)x, (T*)x_bar, (const T*)x0, (const T*)w, (T)tau, (T)th, (T)lo, (T)hi, inv_tau, P.slot(0)};
+    };
+    return pick_store<CpPrimalWLS, CpPrimalWLSRes>(store, [&]<template <typename, int> class E>() {
         return run_DT<E>(c, vec, march_ok(g, d, vec), args, P, out, store);
     });
 }

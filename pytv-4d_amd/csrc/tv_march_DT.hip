@@ -34,5 +34,8 @@ int DT_march(Call& c, const CpPrimalProxArgs<float>& a, bool store) {
 int DT_march(Call& c, const CpPrimalKLArgs<float>& a, bool store) {
     return pick_store<CpPrimalKL, CpPrimalKLRes>(store, [&]<template <typename, int> class E>() { return launch_DT_march<E>(c, a); });
 }
+int DT_march(Call& c, const CpPrimalWLSArgs<float>& a, bool store) {
+    return pick_store<CpPrimalWLS, CpPrimalWLSRes>(store, [&]<template <typename, int> class E>() { return launch_DT_march<E>(c, a); });
+}
 int DT_march(Call& c, const GapDTArgs<float>& a) { return launch_DT_march<GapDT>(c, a); }
 }  // namespace tvm

@@ -631,6 +631,52 @@ template <typename T, int V, bool STORE> struct CpPrimalKLT : CpPrimalKLArgs<T> 
 template <typename T, int V> using CpPrimalKL = CpPrimalKLT<T, V, true>;
 template <typename T, int V> using CpPrimalKLRes = CpPrimalKLT<T, V, false>;
 
+// Chambolle-Pock primal step for a WEIGHTED quadratic data term with a BOX: F(x) = 1/2 sum w (x - x0)^2 + indicator(lo <= x <= hi), with a
+// per-voxel weight w >= 0 (tv_cp_primal_wls; w = 0: the voxel is unknown and TV fills it in -- inpainting, Chambolle & Pock 2011, section
+// 6.3; w = 1 / sigma^2: heteroscedastic least squares).  F is separable, so the prox of tau F is the clamp of the quadratic's prox.  With
+// v = x - tau D^T q and c = tau w / (1 + tau w):
+//   x_new = clamp(v - c (v - x0), lo, hi)
+// -- this form, not (v + tau w x0) / (1 + tau w), for what it makes exact: w == 0 gives c == 0 and x_new = clamp(v) bit for bit; v == x0 gives
+// x0 bit for bit, so a constant image inside the box with q = 0 is left where it is and its residual is exactly 0.  One divide, one fused
+// multiply-add, one three-way median per element; no branch.  lo / hi may be -inf / +inf.
+//   STORE:  x_bar = x_new + theta (x_new - x);  x = x_new;  sum 1/2 w (x_new - x0)^2 in fp64                  Nd + 5 words per voxel
+//   !STORE: reduce-only -- sum ((x - x_new) / tau)^2, the fixed-point residual of the fidelity block; x, x0, w read, nothing written (Nd + 3)
+// Pads stay zero: r, x, x0 and w are zero there, so x_new = clamp(0), and the entry point takes boxes with lo <= 0 <= hi only.
+// The caller's contract: w finite and >= 0, tau w finite.
+__device__ __forceinline__ float  tclamp3(float v, float lo, float hi)    { return __builtin_amdgcn_fmed3f(v, lo, hi); }
+__device__ __forceinline__ double tclamp3(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+template <typename T> struct CpPrimalWLSArgs { T* x; T* x_bar; const T* x0; const T* w; T tau, theta, lo, hi; double inv_tau; double* partials; };
+template <typename T, int V, bool STORE> struct CpPrimalWLST : CpPrimalWLSArgs<T> {
+    static constexpr bool REDUCES = true;
+    __device__ __forceinline__ double operator()(long long off, const Vec<T, V>& r) const {
+        const Vec<T, V> xv = vload_s<T, V>(this->x + off), x0v = vload_s<T, V>(this->x0 + off), wv = vload_s<T, V>(this->w + off);
+        Vec<T, V> xn, xb;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const T v = xv.v[i] - this->tau * r.v[i];
+            const T tw = this->tau * wv.v[i];
+            const T c = tw / (T(1) + tw);
+            xn.v[i] = tclamp3(v - c * (v - x0v.v[i]), this->lo, this->hi);
+            if (STORE) {
+                xb.v[i] = xn.v[i] + this->theta * (xn.v[i] - xv.v[i]);
+                const double e = (double)xn.v[i] - (double)x0v.v[i];
+                acc += 0.5 * (double)wv.v[i] * e * e;
+            } else {
+                const double d = ((double)xv.v[i] - (double)xn.v[i]) * this->inv_tau;
+                acc += d * d;
+            }
+        }
+        if (STORE) {
+            vstore_s<T, V>(this->x + off, xn);
+            vstore_s<T, V>(this->x_bar + off, xb);
+        }
+        return acc;
+    }
+};
+template <typename T, int V> using CpPrimalWLS = CpPrimalWLST<T, V, true>;
+template <typename T, int V> using CpPrimalWLSRes = CpPrimalWLST<T, V, false>;
+
 // =============================================================================================
 // duality gap of 1/2 |x - x0|^2 + lambda |D x|_{2,1} at (x, qs = qscale q), reduce-only (tv_dual_gap): with gd = D^T qs
 //   gap = sum_sites [ 1/2 (x - x0 + gd)^2 + lambda |D x|_2 - <qs, D x> ]      both parts >= 0 site by site for |qs|_2 <= lambda

@@ -22,9 +22,9 @@ from . import solvers            # noqa: E402
 from . import slab               # noqa: E402
 from . import restoration        # noqa: E402
 from . import utils              # noqa: E402
-from .restoration import denoise_tv_chambolle, denoise_tv_huber, denoise_tv_poisson, denoise_tv_robust   # noqa: E402
+from .restoration import denoise_tv_chambolle, denoise_tv_huber, denoise_tv_poisson, denoise_tv_robust, denoise_tv_weighted   # noqa: E402
 
-__all__ = ["tv_GPU", "tv_operators_GPU", "solvers", "slab", "restoration", "utils", "denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber"]
+__all__ = ["tv_GPU", "tv_operators_GPU", "solvers", "slab", "restoration", "utils", "denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted"]
 
 
 def __getattr__(name):

@@ -92,6 +92,7 @@ _SIGNATURES = {
     "tv_cp_primal_prox": (ctypes.c_int, [_G] + [_c_void_p] * 6 + [ctypes.c_int32] + [ctypes.c_double] * 3
                           + [ctypes.c_int32, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_primal_kl": (ctypes.c_int, [_G] + [_c_void_p] * 6 + [ctypes.c_double] * 2 + [ctypes.c_int32, _c_double_p, _c_void_p, _c_void_p]),
+    "tv_cp_primal_wls": (ctypes.c_int, [_G] + [_c_void_p] * 7 + [ctypes.c_double] * 4 + [ctypes.c_int32, _c_double_p, _c_void_p, _c_void_p]),
     "tv_dual_gap": (ctypes.c_int, [_G] + [_c_void_p] * 7 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_dual_residual": (ctypes.c_int, [_G] + [_c_void_p] * 4 + [ctypes.c_double, ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_dual_huber": (ctypes.c_int, [_G] + [_c_void_p] * 4 + [ctypes.c_double] * 3 + [_c_double_p, _c_void_p, _c_void_p]),

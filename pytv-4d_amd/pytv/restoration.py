@@ -7,10 +7,11 @@ Its iteration (Chambolle 2004) differs from Chambolle-Pock 2011, so iterates dif
 """
 import torch
 
-from .solvers import AcceleratedChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock, RobustChambollePock
+from .solvers import (AcceleratedChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock, RobustChambollePock,
+                      WeightedChambollePock)
 from .tv_operators_GPU import _to_device
 
-__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber"]
+__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted"]
 
 
 def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
@@ -100,6 +101,37 @@ def denoise_tv_poisson(image, weight=1.0, rel_res=1e-2, max_num_iter=400, *, sch
     else:
         raise ValueError("denoise_tv_poisson: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
     cp = PoissonChambollePock(vol.contiguous(), float(weight), scheme=scheme, reg_z_over_reg=1.0, tau=tau)
+    cp.run_until(rel_res, max_num_iter, check_every)
+    out = cp.result().reshape(x.shape)
+    return out if was_torch else out.detach().cpu().numpy()
+
+
+def denoise_tv_weighted(image, weights, weight=0.1, lower=None, upper=None, rel_res=1e-2, max_num_iter=400, *, scheme="upwind", tau=None,
+                        check_every=10):
+    """Total-variation denoising / INPAINTING of a 2-D (rows, cols) or 3-D (planes, rows, cols) image with a per-pixel data weight and
+    optional bounds: minimises 1/2 sum weights (u - f)^2 + weight * TV(u) over lower <= u <= upper.
+
+    weights : an array of the image's shape.  bool: True = the pixel is known, False = unknown (a dead detector pixel, a masked region: TV
+              fills it in, whatever value the image holds there); floating point: finite and >= 0, e.g. 1 / variance per pixel.
+    weight  : denoising weight (larger = smoother), as in ``denoise_tv_chambolle`` (which is ``weights`` = 1 everywhere, no bounds).
+    lower, upper : bounds on the result that hold exactly (non-negativity, a normalised range); None = none on that side.
+    rel_res : stop when the optimality residual has dropped to rel_res times that of the start (``WeightedChambollePock.run_until``),
+              checked every ``check_every`` iterations, or after ``max_num_iter`` iterations.
+    tau     : the primal step; None = the balanced default of ``WeightedChambollePock``.
+    Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point."""
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    if x.dim() == 2:
+        vol = x.reshape(1, 1, *x.shape)
+    elif x.dim() == 3:
+        vol = x.reshape(x.shape[0], 1, x.shape[1], x.shape[2])
+    else:
+        raise ValueError("denoise_tv_weighted: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
+    w = torch.as_tensor(weights, device=x.device)
+    if tuple(w.shape) != tuple(x.shape):
+        raise ValueError("denoise_tv_weighted: weights must have the shape of the image, %r (got %r)" % (tuple(x.shape), tuple(w.shape)))
+    cp = WeightedChambollePock(vol.contiguous(), float(weight), w.reshape(vol.shape), lower=lower, upper=upper, scheme=scheme,
+                               reg_z_over_reg=1.0, tau=tau)
     cp.run_until(rel_res, max_num_iter, check_every)
     out = cp.result().reshape(x.shape)
     return out if was_torch else out.detach().cpu().numpy()

@@ -15,6 +15,8 @@ fused HIP kernels (include/pytv4d.h):
                         extrapolation)  (Nd+4): TV-L1 and TV-Huber for impulse noise (Chambolle & Pock 2011, section 6.2.2)
     PoissonChambollePock tv_cp_dual on the extrapolated point + tv_cp_primal_kl (D^T, cancellation-free prox of the Kullback-Leibler
                         fidelity, extrapolation)  (Nd+4): TV-KL for photon-counting data
+    WeightedChambollePock tv_cp_dual on the extrapolated point + tv_cp_primal_wls (D^T, prox of a per-voxel weighted quadratic fidelity
+                        clamped to a box, extrapolation)  (Nd+5): inpainting of unknown voxels, heteroscedastic data, bounds on the iterate
     HuberChambollePock  tv_cp_dual_huber on the extrapolated point (shrink + projection, Huber partial) + tv_cp_primal_accel with fixed steps:
                         the Huber-TV regulariser against staircasing, linearly convergent (Chambolle & Pock 2011, Algorithm 3)
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
@@ -35,7 +37,7 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "HuberChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
            "accel_schedule", "cp_linear_steps", "auto_pitch", "operator_norm_sq"]
 
 
@@ -576,7 +578,7 @@ class _SlabProblem:
     def _run_until_residual(self, rel_res, max_iter, check_every):
         """``run`` in blocks of ``check_every`` until ``residuals()["total"]`` <= rel_res**2 * ``initial_residual()`` at a check or ``max_iter``
         iterations are done (the solvers without a duality gap: ``ChambollePockOperator``, ``RobustChambollePock``,
-        ``PoissonChambollePock``)."""
+        ``PoissonChambollePock``, ``WeightedChambollePock``)."""
         import numpy as np
         rel_res, max_iter, check_every = float(rel_res), int(max_iter), int(check_every)
         if check_every < 1 or max_iter < 0:
@@ -1156,7 +1158,7 @@ class ChambollePock(_SlabProblem):
 # =================================================================================================
 class _ExtrapolatedCP(_SlabProblem):
     """What the Chambolle-Pock solvers with the state (x, x_bar, q) share (``AcceleratedChambollePock``, ``RobustChambollePock``,
-    ``PoissonChambollePock``): the state
+    ``PoissonChambollePock``, ``WeightedChambollePock``): the state
     and its halo planes, the dual half of an iteration -- tv_cp_dual on the extrapolated point x_bar -- and the loop around ``step``.  A
     subclass validates its steps (``cp_step_pair`` on ``L2``), calls ``_alloc_state`` and supplies ``step``: ``_dual_half`` + its primal
     kernel.  Per-step scalars: the slots of ``ChambollePock``."""
@@ -1451,7 +1453,7 @@ class HuberChambollePock(_ExtrapolatedCP):
 # =================================================================================================
 class _FixedPointResiduals:
     """The optimality residual of the solvers whose fidelity has a pointwise prox but no cheap duality gap (``RobustChambollePock``,
-    ``PoissonChambollePock``): tv_cp_dual_residual for the dual block, the class's primal kernel in residual mode for the fidelity block.
+    ``PoissonChambollePock``, ``WeightedChambollePock``): tv_cp_dual_residual for the dual block, the class's primal kernel in residual mode for the fidelity block.
     The class supplies ``_prox(q, qp, qn, x, x_bar, theta, flags, out_ptr)`` (its primal entry point) and ``_fidelity_value()``, calls
     ``_init_residuals`` at the end of its constructor, and keeps ``residuals`` / ``run_until`` with docstrings of its own."""
 
@@ -1692,6 +1694,158 @@ class PoissonChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         (x0, q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
         Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
         ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 2-word pass and the fidelity reduction.
+        """
+        return self._run_until_residual(rel_res, max_iter, check_every)
+    run_until.__doc__ += _RES_DOC
+
+
+# =================================================================================================
+class WeightedChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
+    """min_{lower <= x <= upper} 1/2 sum_i w_i (x_i - x0_i)^2 + regularization * TV(x) with a PER-VOXEL DATA WEIGHT w >= 0 and an optional
+    BOX on the iterate, with Algorithm 1 of Chambolle & Pock 2011 (theta = 1, fixed steps).
+
+        w_i = 0          the voxel is UNKNOWN -- a dead detector module, a masked frame, a metal trace, a missing projection -- and TV fills
+                         it in from its neighbours: the inpainting model of section 6.3 of the paper (x0 there is never looked at)
+        w_i = 1 / s_i^2  heteroscedastic least squares: every voxel is trusted according to its own noise level
+        lower, upper     bounds that hold EXACTLY on every iterate: non-negative attenuation, a normalised range [0, 1]
+
+    State: x, x_bar (images), q (gradient); x = x_bar = clamp(x0), q = 0 at the start.  One iteration:
+
+        q     <- proj_{|.|_2 <= reg}(q + sigma D x_bar)                             tv_cp_dual on x_bar         (2 Nd + 1 words per voxel)
+        v      = x - tau D^T q;  c = tau w / (1 + tau w)
+        x_new <- clamp(v - c (v - x0), lower, upper)                                the prox of a separable term: the quadratic's, clamped
+        x_bar <- 2 x_new - x;  x <- x_new                                           tv_cp_primal_wls, one pass  (Nd + 5)
+
+    -- 3 Nd + 6 words per voxel, the loop of ``RobustChambollePock`` with one more array read (w).  The prox is taken in the form above
+    rather than (v + tau w x0) / (1 + tau w): a voxel with w = 0 is clamp(v) bit for bit, and a constant image inside the box is a fixed
+    point bit for bit.  Sharded (``slab``): as ``RobustChambollePock``; w needs no halo plane.
+
+    THE SHIFT.  The kernel takes boxes that contain 0 (the pad elements of pitched arrays must stay 0).  TV and the data term do not change
+    when x, x0 and the box are shifted by one constant, so for another box the solver works on x0 - shift with the box
+    [lower - shift, upper - shift], ``shift`` = min(max(0, lower), upper) -- the point of the box nearest to 0; 0 for every box that
+    contains 0.  ``self.shift`` holds it, ``result()`` adds it back; ``self.x`` / ``self.x0`` / ``self.lower`` / ``self.upper`` are the
+    SHIFTED state the kernels see.  (fp32: x0 - shift is rounded once, at construction.)
+
+    STEPS.  tau sigma L^2 <= 1 with L^2 = ``normal_spectral_bound``; both default to 1 / sqrt(L^2), one given: the other is 1 / (L^2 times
+    it).  ``residuals()`` gives the fixed-point (KKT) residual of the saddle problem, ``run_until`` stops on it.
+
+    Not built (out of scope here): an ACCELERATED or linear-rate schedule -- the data term is min(w)-strongly convex only where every
+    w > 0, and with gamma = min w the schedule of Algorithm 2 did not beat the fixed steps reliably in a NumPy restatement, so this solver
+    runs Algorithm 1 only --, a one-sweep / fix-up form of the iteration, hipGraph capture, a persistent small-volume form, the placement
+    tuner / arena of ``ChambollePock``, an ``x_init`` argument, and per-voxel weights on the TV term (``mask_static`` weights its time
+    component only).
+
+    Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, 1/2 sum w (x_new - x0)^2 in slot ``F``."""
+
+    def __init__(self, x0, regularization, weights, lower=None, upper=None, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0,
+                 mask_static=False, factor_reg_static=0, tau=None, sigma=None, slab=None, pitch="auto"):
+        """x0: the data, finite.  weights: a bool array (True = known: stored as 1, False = unknown: 0) or a floating-point array, finite
+        and >= 0, of x0's shape (this rank's slab); kept in the layout of x0.  lower, upper: the box, None = no bound on that side.
+        ValueError: a wrong shape, weights that are negative or not finite, x0 not finite, lower > upper or a NaN bound, weights that are
+        zero everywhere (on every rank: nothing ties the solution down), tau * max(w) not finite in the dtype of x0.  Sharded: the checks
+        of the arrays are collective, every rank raises.  tau, sigma: see the class docstring -- tau * sigma * L^2 > 1 + 1e-12 raises
+        ValueError.  pitch: see ``_SlabProblem``."""
+        lo = -math.inf if lower is None else float(lower)
+        hi = math.inf if upper is None else float(upper)
+        if math.isnan(lo) or math.isnan(hi) or lo > hi:
+            raise ValueError("WeightedChambollePock: lower <= upper is required (got lower=%r, upper=%r)" % (lower, upper))
+        self.shift = min(max(0.0, lo), hi)
+        if self.shift != 0.0 and isinstance(x0, torch.Tensor):
+            x0 = x0 - self.shift
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
+        self.lower, self.upper = lo - self.shift, hi - self.shift
+        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        w = torch.as_tensor(weights, device=self.device)
+        if tuple(w.shape) != tuple(x0.shape):
+            raise ValueError("WeightedChambollePock: weights must have the shape of x0, %r (got %r)" % (tuple(x0.shape), tuple(w.shape)))
+        if not (w.dtype == torch.bool or w.dtype.is_floating_point):
+            raise ValueError("WeightedChambollePock: weights must be bool or floating point (got %s)" % w.dtype)
+        w = w.to(self.dtype)
+        wlo, whi = torch.aminmax(w)                      # NaN propagates through both
+        xlo, xhi = torch.aminmax(x0)
+        flags = torch.stack([~((wlo >= 0) & torch.isfinite(whi)), ~(torch.isfinite(xlo) & torch.isfinite(xhi))]).to(torch.float64)
+        wmax = whi.to(torch.float64).nan_to_num(nan=0.0).reshape(1)
+        self.slab.allreduce_sum_(flags)
+        self.slab.allreduce_max_(wmax)
+        bad_w, bad_x0 = (float(v) != 0.0 for v in flags.cpu().tolist())
+        if bad_w:
+            raise ValueError("WeightedChambollePock: weights must be finite and >= 0 everywhere")
+        if bad_x0:
+            raise ValueError("WeightedChambollePock: x0 must be finite everywhere (mark unknown voxels with a weight of 0 and any finite value)")
+        wmax = float(wmax.item())
+        if wmax == 0.0:
+            raise ValueError("WeightedChambollePock: the weights are zero everywhere -- no voxel is known")
+        if not self.tau * wmax <= torch.finfo(self.dtype).max:
+            raise ValueError("WeightedChambollePock: tau * max(weights) = %g is not finite in %s" % (self.tau * wmax, self.dtype))
+        self.w = self.image_copy(w)
+        self._alloc_state()
+        self._clamp_start()
+        self._init_residuals()
+
+    def _clamp_start(self):
+        """x = x_bar = clamp(x0) (the pads of pitched arrays stay 0: the shifted box contains 0)"""
+        self.x.clamp_(self.lower, self.upper)
+        self.x_bar.copy_(self.x)
+
+    def reset(self):
+        """Back to the state of a fresh solver: x = x_bar = clamp(x0), q = 0, iteration 0."""
+        super().reset()
+        self._clamp_start()
+
+    def result(self):
+        """The iterate of the ORIGINAL problem (``shift`` added back) as a dense (Nz, M, Ny, Nx) tensor; with ``shift`` = 0 and dense state
+        it is ``self.x`` itself, otherwise a copy."""
+        out = super().result()
+        return out + self.shift if self.shift != 0.0 else out
+
+    def _prox(self, q, qp, qn, x, x_bar, theta, flags, out_ptr):
+        _nv.check(self.lib.tv_cp_primal_wls(self.geo.ref, _nv.ptr(q), _nv.ptr(qp), _nv.ptr(qn), _nv.ptr(x), _nv.ptr(x_bar), _nv.ptr(self.x0),
+                                            _nv.ptr(self.w), self.lower, self.upper, self.tau, theta, flags, out_ptr, _nv.ptr(self.ws),
+                                            self.stream))
+
+    def step(self, out=None):
+        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
+        1/2 sum w (x_new - x0)^2 in slot F; defaults to an internal scratch."""
+        out = self._scratch if out is None else out
+        self._dual_half(self.sigma, out)
+        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[self.F:self.F + 1].data_ptr())
+        self.it += 1
+
+    def run(self, n_iter, record_loss=True):
+        """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
+        None.  Row k is 1/2 sum w (x_{k+1} - x0)^2 + reg |D x_bar_k|_{2,1}: the TV term is that of the extrapolated point the dual step
+        saw -- a progress indicator in the slots of ``ChambollePock``'s history; the objective of the current iterate is
+        ``residuals()["fid"] + reg * residuals()["tv"]``."""
+        return self._run(n_iter, record_loss)
+
+    _RES_DOC = """(x, q) is a saddle point of  min_{lower <= x <= upper} max_{|q|_2 <= reg}  F(x) + <D x, q>,  F(x) = 1/2 sum w (x - x0)^2  (whose x
+        solves the problem) iff it is a fixed point of both updates of the iteration.  The residual R = R_x + R_q:
+            R_x = |x - prox_{tau F}(x - tau D^T q)|^2 / tau^2                zero iff -D^T q is in the subdifferential of F + box at x:
+                                                                             tv_cp_primal_wls in residual mode, Nd + 3 words per voxel
+            R_q = |q - proj(q + sigma D x)|^2 / sigma^2                      zero iff q is in the subdifferential of reg |.|_2 at D x:
+                                                                             tv_cp_dual_residual, Nd + 1 words per voxel
+        both summed site by site in fp64 by reduce-only kernels.  fp32: R_x is resolved down to about (eps_fp32 |x| / tau)^2 per voxel."""
+
+    def _fidelity_value(self):
+        """1/2 sum w (x - x0)^2 of this rank as a 0-d fp64 device tensor: element-wise torch arithmetic in the image dtype, summed in fp64.
+        Called once per check, never inside the loop (the loop's own fidelity scalar comes out of tv_cp_primal_wls)."""
+        e = torch.sub(self.x, self.x0)
+        return 0.5 * e.mul_(e).mul_(self.w).sum(dtype=torch.float64)
+
+    def residuals(self):
+        """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": 1/2 sum w (x - x0)^2} of the current pair (x, q) as Python
+        floats, between ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the
+        scalars, one host synchronisation.  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._residual_dict(self._residual_scalars())
+    residuals.__doc__ += _RES_DOC
+
+    def run_until(self, rel_res, max_iter, check_every=10):
+        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
+        first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the pair the constructor left
+        (clamp(x0), q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
+        Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
+        ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 3-word pass and the fidelity reduction.
         """
         return self._run_until_residual(rel_res, max_iter, check_every)
     run_until.__doc__ += _RES_DOC

@@ -336,6 +336,42 @@ int tv_cp_dual_huber(const tv_geom* g, const void* x, const void* x_prev, const 
 int tv_dual_gap_huber(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
                       const void* q_next, const void* x0, double lambda, double alpha, double* out, void* ws, void* stream);
 
+/* Dual step of Chambolle-Pock for the SPATIALLY ADAPTIVE regulariser: a per-voxel weight g_i >= 0 on the TV term,
+ *   P(x) = 1/2 |x - x0|^2 + lambda sum_i g_i |D x|_{2,i}
+ * (noise-adaptive lambda, edge-stopping weights g = 1 / (1 + (|D x0| / kappa)^2), protected regions g = 0).  The conjugate differs from
+ * plain TV's only in the radius of the ball a site's dual vector is projected onto: r_i = lambda g_i instead of lambda.  At each site
+ *   v = q + sigma_D D x per channel,  n = |v|_2;   q <- v where n <= r_i,  v * (r_i / n) beyond        (a select, not a multiply by 1)
+ *   *wtv (device fp64) = sum_i g_i |D x|_{2,i} of the local planes, accumulated in fp64: the loss is fid + lambda * *wtv.
+ * For finite inputs with g >= 0: a site inside its ball keeps q = v bit for bit; a site with g_i = 0 ends with q = +-0 in every channel;
+ * the result is never NaN or Inf (n = 0 with r = 0 included: r / n is used only where n > r); |q|_2 <= r_i up to rounding afterwards.
+ * gw is an image-like array of the geometry's dtype stored exactly like x0: the local planes of the slab, pitched with the others (pads
+ * zero), NO halo plane (the projection is local), part of the 16-byte alignment test.  g FINITE AND >= 0 IS THE CALLER'S CONTRACT: the
+ * kernel does not check it (pytv.solvers.AdaptiveTVChambollePock does, once, at construction).
+ * 2 Nd + 2 words per voxel; q is written in place, nothing else but wtv and ws.  x_prev / x_next, alignment and dispatch as tv_cp_dual:
+ * four schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays, mask_static / time_factor / time_weight_vol, z-slabs; fp32
+ * planes of >= 4 MiB take the plane-marching kernel (NOT downwind / central / hybrid WITH 16 FRAMES: those instantiations would spill to
+ * scratch and do not exist; the one-site kernel runs there).  The primal half of the iteration is tv_cp_primal_accel.
+ * TV_E_ARG: a NULL array ("<name> is NULL", gw included), lambda or sigma_D not finite and > 0, a tv_geom of another interface version;
+ * a missing halo plane is TV_E_HALO ("x_prev: ..." / "x_next: ..."); all checks precede any device access. */
+int tv_cp_dual_wtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q, const void* gw,
+                   double sigma_D, double lambda, double* wtv, void* ws, void* stream);
+
+/* Duality-gap certificate of the spatially adaptive model above for an iterate x and a dual variable q with |q|_2 <= lambda g_i per site
+ * (what tv_cp_dual_wtv leaves).  Dual(q) = <gd, x0> - 1/2 |gd|^2 with gd = D^T q.  Over the local planes
+ *   out[0] = sum_i g_i |D x|_{2,i}
+ *   out[1] = 1/2 |x - x0|^2
+ *   out[2] = sum_sites [ 1/2 (x - x0 + gd)^2  +  (lambda g_i |D x|_2 - <q, D x>) ]  =  P(x) - Dual(q)
+ * Both parts of a site's term are >= 0 for a feasible q.  Accumulated site by site in that form in fp64, never as P - Dual, not clamped.
+ * The caller has P = out[1] + lambda * out[0], Dual = P - out[2], and 1/2 |x - x*|^2 <= out[2].
+ * REDUCE-ONLY: nothing is written except out (three device fp64 words) and ws.  x_prev / x_next as in tv_cp_dual, q_prev / q_next as in
+ * tv_dual_gap; gw as in tv_cp_dual_wtv (no halo plane; finite and >= 0 is the caller's contract, not checked); slab partials add up to
+ * the unsharded scalars.  Every geometry of tv_dual_gap: one launch of the one-site-per-thread kernel, Nd + 3 words per voxel, large
+ * planes too (the call is made once per convergence check; there is no plane-marching form).
+ * TV_E_ARG: a NULL array ("<name> is NULL", gw included), lambda not finite and > 0, a tv_geom of another interface version; a missing
+ * halo plane is TV_E_HALO ("x_prev: ..." / "x_next: ..." / "q_prev: ..." / "q_next: ..."); all checks precede any device access. */
+int tv_dual_gap_wtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                    const void* q_next, const void* x0, const void* gw, double lambda, double* out, void* ws, void* stream);
+
 /* One-sweep form of the same iteration (all four schemes; fp32, nx % 4 == 0, nx >= 64,
  * any m: more than 8 frames are processed as time windows of 8): q is read and written ONCE per
  * iteration.  x is ping-ponged.

@@ -348,19 +348,24 @@ template <template <typename, int> class On, template <typename, int> class Off,
 // (CpDual: 164 / 340 bytes of scratch per lane).  CpDualHuber is not instantiated for these: launch_D_march leaves them out and
 // tv_cp_dual_huber keeps them on the one-site kernel, both by this ONE rule.
 constexpr bool wide16(int scheme, int m) { return m == 16 && (scheme == CENTRAL || scheme == HYBRID); }
+// CpDualWtv reads one more array per site: with 16 frames it spills in the downwind scheme as well (64 / 796 / 452 bytes of scratch per lane
+// for downwind / central / hybrid; upwind: none -- profiles/adaptive_tv_regs.txt), so only upwind marches with M = 16 under that epilogue.
+// launch_D_march and tv_cp_dual_wtv share this ONE rule.
+constexpr bool wtv_spill16(int scheme, int m) { return m == 16 && scheme != UPWIND; }
 
 namespace tv {      // the epilogue argument structs of tv_stencil.h
 template <typename T> struct StoreDArgs; template <typename T> struct CpDualArgs; template <typename T> struct CpDualHuberArgs;
 template <typename T> struct AdmmZUArgs; template <typename T> struct GapDArgs; template <typename T> struct StoreDTArgs;
 template <typename T> struct AxpyDTArgs; template <typename T> struct CpPrimalArgs; template <typename T> struct CpPrimalAccelArgs;
 template <typename T> struct CpPrimalProxArgs; template <typename T> struct CpPrimalKLArgs; template <typename T> struct GapDTArgs;
-template <typename T> struct CpPrimalWLSArgs;
+template <typename T> struct CpPrimalWLSArgs; template <typename T> struct CpDualWtvArgs;
 }
 namespace tvm {
 // D x with the epilogue whose arguments are given (fp32): one overload per epilogue, each a line in tv_march_D.hip
 int D_march(Call& c, const StoreDArgs<float>& a);
 int D_march(Call& c, const CpDualArgs<float>& a);
 int D_march(Call& c, const CpDualHuberArgs<float>& a);       // not where wide16(scheme, M)
+int D_march(Call& c, const CpDualWtvArgs<float>& a);         // not where wtv_spill16(scheme, M)
 int D_march(Call& c, const AdmmZUArgs<float>& a);
 // duality gap, reduce-only (tv_dual_gap): the D^T-side pass (DT_march with GapDTArgs) writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2,
 // the D-side pass (same grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to

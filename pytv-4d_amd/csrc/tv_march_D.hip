@@ -3,14 +3,15 @@
 #include "tv_stencil.h"
 #include "tv_march.h"
 
-// NO_WIDE16: leave out the (scheme, M) of wide16() (tv_host.h); the caller keeps those geometries on the one-site kernel
-template <template <int, typename, int> class EpiT, bool NO_WIDE16 = false, typename Args>
+// SKIP: the (scheme, M) to leave out -- wide16() or wtv_spill16() of tv_host.h; the caller keeps those geometries on the one-site kernel
+constexpr bool skip_none(int, int) { return false; }
+template <template <int, typename, int> class EpiT, bool (*SKIP)(int, int) = skip_none, typename Args>
 static int launch_D_march(Call& c, const Args& args) {
     const int zc = march_zchunk(c.d);
     const LC lc = march_cfg(c.d, zc);
     c.nblocks = lc.nblocks;
     return dispatch_scheme_m(MarchMs{}, c.g->scheme, c.d.m, kNoMarchSM, [&]<int S, int M>() -> int {
-        if constexpr (NO_WIDE16 && wide16(S, M)) {
+        if constexpr (SKIP(S, M)) {
             return fail(TV_E_ARG, kNoMarchSM);
         } else {
             EpiT<S, float, 4> epi{args};
@@ -25,7 +26,8 @@ static int launch_D_march(Call& c, const Args& args) {
 namespace tvm {
 int D_march(Call& c, const StoreDArgs<float>& a) { return launch_D_march<StoreD>(c, a); }
 int D_march(Call& c, const CpDualArgs<float>& a) { return launch_D_march<CpDual>(c, a); }
-int D_march(Call& c, const CpDualHuberArgs<float>& a) { return launch_D_march<CpDualHuber, true>(c, a); }
+int D_march(Call& c, const CpDualHuberArgs<float>& a) { return launch_D_march<CpDualHuber, wide16>(c, a); }
+int D_march(Call& c, const CpDualWtvArgs<float>& a) { return launch_D_march<CpDualWtv, wtv_spill16>(c, a); }
 int D_march(Call& c, const AdmmZUArgs<float>& a) { return launch_D_march<AdmmZU>(c, a); }
 int D_march(Call& c, const GapDArgs<float>& a) { return launch_D_march<GapD>(c, a); }
 int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,

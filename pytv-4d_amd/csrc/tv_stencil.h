@@ -315,6 +315,50 @@ template <int S, typename T, int V> struct CpDualHuber : CpDualHuberArgs<T> {
     }
 };
 
+// Chambolle-Pock dual update for the SPATIALLY ADAPTIVE regulariser lambda sum g_i |D x|_{2,i}, g_i >= 0 per voxel (tv_cp_dual_wtv): the
+// conjugate differs from plain TV's only in the radius of the ball a site's dual vector is projected onto, r = lambda g_i.  The arithmetic
+// of one site: v = q + sigma D x per channel, n = |v|_2, r per column; the new q is v * scale with scale SELECTED per column:
+//   r = 0 (g_i = 0)  ->  the constant 0: q = +-0 in every channel, also where n rounds to 0
+//   n <= r           ->  the constant 1: v * 1 is v bit for bit (IEEE), never v times a COMPUTED factor that may round off 1
+//   n > r            ->  r / n, evaluated for the result only here, where n > r > 0: no 0 / 0 or x / 0 reaches q
+// Returns sum over the columns of g_i |D x|_2 in fp64.  gw is the weight at the site (read once: non-temporal).  cp_dual_site's sibling.
+template <int S, typename T, int V>
+__device__ __forceinline__ double cp_dual_wtv_site(const DG& g, const T* base, const Vec<T, V> (&o)[8], const Vec<T, V>& gw, T sigma, T lambda,
+                                                   Vec<T, V> (&v)[8], Vec<T, V>& scale) {
+    Vec<T, V> vs = vsplat<T, V>(T(0));
+    for_each_channel<S>(g, [&](auto slot, int ch) {
+        constexpr int k = decltype(slot)::value;
+        v[k] = vload_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z) + sigma * o[k];
+        vs = vs + v[k] * v[k];
+    });
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const T n = tsqrt(vs.v[i]), r = lambda * gw.v[i];
+        acc += (double)gw.v[i] * (double)tsqrt(ds.v[i]);
+        scale.v[i] = (r > T(0)) ? ((n > r) ? r / n : T(1)) : T(0);
+    }
+    return acc;
+}
+template <typename T> struct CpDualWtvArgs { T* q; const T* gw; T sigma, lambda; double* partials; };
+template <int S, typename T, int V> struct CpDualWtv : CpDualWtvArgs<T> {
+    static constexpr bool REDUCES = true;
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        const long long inpl = (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        T* base = this->q + (long long)c.zl * g.s_dz + inpl;
+        const Vec<T, V> gv = vload_s<T, V>(this->gw + (long long)c.zl * g.s_z + inpl);
+        Vec<T, V> v[8];
+        Vec<T, V> scale;
+        const double acc = cp_dual_wtv_site<S, T, V>(g, base, o, gv, this->sigma, this->lambda, v, scale);
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            constexpr int k = decltype(slot)::value;
+            vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);
+        });
+        return acc;
+    }
+};
+
 // ADMM: v = Dx + u;  z = v * max(0, 1 - thresh/|v|);  u = v - z.   tform: the first array receives t = z - u_new
 // (= 2 z - v) instead of z: the next right-hand side x0 + rho D^T (z - u) then reads ONE gradient array
 template <typename T> struct AdmmZUArgs { T* z; T* u; T thresh; double* partials; int tform = 0; };
@@ -748,6 +792,26 @@ __device__ __forceinline__ void gap_terms_huber(const Vec<T, V> (&o)[8], const V
         a_gap += 0.5 * r * r + (n <= k.alpha ? k.l_over_2a * sq : k.lambda * (n - 0.5 * k.alpha) - dot + k.a_over_2l * qq);
     };
     [&]<int... I>(std::integer_sequence<int, I...>) { (column(IC<I>{}), ...); }(std::make_integer_sequence<int, V>{});
+}
+// gap_terms for the spatially adaptive model 1/2 |x - x0|^2 + lambda sum g_i |D x|_{2,i} at (x, q), |q|_2 <= lambda g_i per site
+// (tv_dual_gap_wtv): the radius lambda g_i of the site in place of lambda.  a_wtv receives g_i |D x|_2; the site's gap term is
+// 1/2 (x - x0 + gd)^2 + (lambda g_i |D x|_2 - <q, D x>), both parts >= 0 for a feasible q (Cauchy-Schwarz), never formed as P - Dual.
+template <typename T, int V>
+__device__ __forceinline__ void gap_terms_wtv(const Vec<T, V> (&o)[8], const Vec<T, V> (&qv)[8], const Vec<T, V>& xv, const Vec<T, V>& x0v,
+                                              const Vec<T, V>& gv, const Vec<T, V>& gd, double lambda, double& a_wtv, double& a_fid, double& a_gap) {
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    Vec<T, V> dot = vsplat<T, V>(T(0));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dot = dot + qv[k] * o[k];              // inactive slots are exactly zero in o
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const double gn = (double)gv.v[i] * (double)tsqrt(ds.v[i]);
+        const double e = (double)xv.v[i] - (double)x0v.v[i];
+        const double r = e + (double)gd.v[i];
+        a_wtv += gn;
+        a_fid += 0.5 * e * e;
+        a_gap += 0.5 * r * r + (lambda * gn - (double)dot.v[i]);
+    }
 }
 // D-side pass of the plane-marching form (k_D_march): |D x|_{2,1}, 1/2 |x - x0|^2 and sum (lambda |D x|_2 - <qs, D x>); reads x0 and q once.
 // The D^T-side pass (GapDT) ran BEFORE it on the same grid and left its per-block sums in `partials`: finish() adds to them.

@@ -5,13 +5,17 @@ scikit-image minimises  sum |grad u| + (1 / (2 weight)) |u - f|^2  with forward 
 1/2 |u - f|^2 + weight * TV_upwind(u): the same objective as ``solvers.ChambollePock(f, weight, scheme="upwind")``.
 Its iteration (Chambolle 2004) differs from Chambolle-Pock 2011, so iterates differ; the minimiser is the same.
 """
+import math
+
 import torch
 
-from .solvers import (AcceleratedChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock, RobustChambollePock,
-                      WeightedChambollePock)
+from . import _native as _nv
+from .solvers import (AcceleratedChambollePock, AdaptiveTVChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock,
+                      RobustChambollePock, WeightedChambollePock)
 from .tv_operators_GPU import _to_device
 
-__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted"]
+__all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted", "denoise_tv_adaptive",
+           "edge_stopping_weights"]
 
 
 def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
@@ -157,6 +161,69 @@ def denoise_tv_huber(image, weight=0.1, alpha=1.0, rel_gap=1e-4, max_num_iter=20
     else:
         raise ValueError("denoise_tv_huber: 2-D or 3-D images only (use pytv.solvers for 4-D data)")
     cp = HuberChambollePock(vol.contiguous(), float(weight), float(alpha), scheme=scheme, reg_z_over_reg=1.0)
+    cp.run_until(rel_gap, max_num_iter, check_every)
+    out = cp.result().reshape(x.shape)
+    return out if was_torch else out.detach().cpu().numpy()
+
+
+def _as_volume(x, who):
+    """a 2-D (rows, cols) or 3-D (planes, rows, cols) device tensor as the (Nz, 1, Ny, Nx) volume the solvers take"""
+    if x.dim() == 2:
+        return x.reshape(1, 1, *x.shape).contiguous()
+    if x.dim() == 3:
+        return x.reshape(x.shape[0], 1, x.shape[1], x.shape[2]).contiguous()
+    raise ValueError("%s: 2-D or 3-D images only (use pytv.solvers for 4-D data)" % who)
+
+
+def edge_stopping_weights(image, kappa, *, scheme="upwind"):
+    """The edge-stopping weights g = 1 / (1 + (|grad image|_2 / kappa)^2) of a 2-D (rows, cols) or 3-D (planes, rows, cols) image: 1 where
+    the image is flat, small across an edge whose gradient magnitude exceeds ``kappa`` -- the weighted TV of the segmentation and
+    edge-preserving denoising literature, ``reg_weights`` of ``denoise_tv_adaptive`` / ``AdaptiveTVChambollePock``.
+
+    kappa  : the gradient magnitude, in grey levels per pixel, at which the weight is 1/2; finite and > 0 (ValueError otherwise).
+    scheme : the difference scheme of the gradient, that of the denoising call the weights are meant for.
+    |grad image|_2 is the per-pixel norm over the channels of D image (tv_D + tv_l21, the differences the solver takes); the weights lie
+    in (0, 1].  Returns an array of the input's kind and shape (numpy in -> numpy out, torch in -> device tensor), floating point."""
+    kappa = float(kappa)
+    if not (math.isfinite(kappa) and kappa > 0.0):
+        raise ValueError("edge_stopping_weights: kappa must be finite and > 0")
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    vol = _as_volume(x, "edge_stopping_weights")
+    geo = _nv.Geometry(tuple(vol.shape), scheme, vol.dtype, vol.device, 1.0, 0.0, False, 0)
+    d = torch.empty(geo.grad_shape, dtype=vol.dtype, device=vol.device)
+    norms = torch.empty_like(vol)
+    st = _nv.current_stream(vol.device)
+    _nv.check(_nv.lib().tv_D(geo.ref, _nv.ptr(vol), None, None, _nv.ptr(d), st))
+    _nv.check(_nv.lib().tv_l21(geo.ref, _nv.ptr(d), geo.nd, _nv.ptr(norms), _nv.ptr(geo.scalar()), _nv.ptr(geo.workspace()), st))
+    norms.div_(kappa)
+    g = torch.reciprocal(norms.mul_(norms).add_(1.0)).reshape(x.shape)
+    return g if was_torch else g.detach().cpu().numpy()
+
+
+def denoise_tv_adaptive(image, weight=0.1, reg_weights=None, rel_gap=1e-4, max_num_iter=200, *, scheme="upwind", check_every=10):
+    """SPATIALLY ADAPTIVE total-variation denoising of a 2-D (rows, cols) or 3-D (planes, rows, cols) image: minimises
+    1/2 |u - f|^2 + weight * sum_i reg_weights_i |grad u|_i -- the strength of the TV term varies from pixel to pixel.
+
+    weight      : denoising weight (larger = smoother), as in ``denoise_tv_chambolle``.
+    reg_weights : an array of the image's shape, finite and >= 0; None = all ones (``denoise_tv_chambolle``'s model).  Larger where the
+                  noise is stronger; ``edge_stopping_weights(image, kappa)`` to smooth less across edges; 0 inside a region that must be
+                  left as it is.
+    rel_gap     : stop when the duality gap certifies the answer, gap <= rel_gap * objective at a check
+                  (``AdaptiveTVChambollePock.run_until``: 1/2 |u - u*|^2 <= gap), checked every ``check_every`` iterations, or after
+                  ``max_num_iter`` iterations.
+    Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point."""
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    vol = _as_volume(x, "denoise_tv_adaptive")
+    if reg_weights is None:
+        g = torch.ones_like(vol)
+    else:
+        g = torch.as_tensor(reg_weights, device=x.device)
+        if tuple(g.shape) != tuple(x.shape):
+            raise ValueError("denoise_tv_adaptive: reg_weights must have the shape of the image, %r (got %r)" % (tuple(x.shape), tuple(g.shape)))
+        g = g.reshape(vol.shape)
+    cp = AdaptiveTVChambollePock(vol, float(weight), g, scheme=scheme, reg_z_over_reg=1.0)
     cp.run_until(rel_gap, max_num_iter, check_every)
     out = cp.result().reshape(x.shape)
     return out if was_torch else out.detach().cpu().numpy()

@@ -19,6 +19,9 @@ fused HIP kernels (include/pytv4d.h):
                         clamped to a box, extrapolation)  (Nd+5): inpainting of unknown voxels, heteroscedastic data, bounds on the iterate
     HuberChambollePock  tv_cp_dual_huber on the extrapolated point (shrink + projection, Huber partial) + tv_cp_primal_accel with fixed steps:
                         the Huber-TV regulariser against staircasing, linearly convergent (Chambolle & Pock 2011, Algorithm 3)
+    AdaptiveTVChambollePock  tv_cp_dual_wtv on the extrapolated point (projection onto a per-voxel radius reg * g_i, weighted TV partial)
+                        (2Nd+2) + tv_cp_primal_accel with the accelerated schedule: spatially adaptive TV (noise-adaptive lambda,
+                        edge-stopping weights, protected regions)
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
     ADMM                tv_admm_tu / tv_admm_zu, tv_DT_axpy, tv_normal_op2 (I + rho D^T D from x alone, two dot products) +
                         tv_cg_update (single-reduction CG; textbook tv_cg_step1/2 kept)
@@ -37,7 +40,7 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "AdaptiveTVChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
            "accel_schedule", "cp_linear_steps", "auto_pitch", "operator_norm_sq"]
 
 
@@ -1243,7 +1246,8 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
     placement tuner / arena of ``ChambollePock``, a persistent small-volume form, and the sweep / exchange / fix-up schedule of a sharded slab
     (slabs run the kernel pair) -- at the reference's small shapes the solver pays a launch per kernel against the persistent loop of
     ``ChambollePock`` (DESIGN.md section 3.4).  The Huber-TV regulariser (quadratic below a gradient magnitude alpha, against staircasing;
-    linearly convergent) is ``HuberChambollePock``.
+    linearly convergent) is ``HuberChambollePock``; a per-voxel weight on the TV term (spatially adaptive TV, this schedule) is
+    ``AdaptiveTVChambollePock``.
 
     gamma = 0 gives theta = 1 and constant steps (Algorithm 1 with extrapolation).  The step schedule continues across ``run`` /
     ``run_steps`` / ``step`` calls (``self.it`` counts the iterations done); ``reset()`` starts it again.
@@ -1377,7 +1381,7 @@ class HuberChambollePock(_ExtrapolatedCP):
 
     Not built (out of scope here): a one-sweep / fix-up form of this iteration, a persistent small-volume form, hipGraph capture, the
     placement tuner / arena of ``ChambollePock``, a plane-marching form of the gap kernel, and Huber-TV under the L1 / Huber / KL data terms
-    of ``RobustChambollePock`` / ``PoissonChambollePock``.
+    of ``RobustChambollePock`` / ``PoissonChambollePock``.  A per-voxel weight on the (plain) TV term is ``AdaptiveTVChambollePock``.
 
     Per-step scalars: the slots of ``ChambollePock`` -- sum h_alpha(|D x_bar|_2) in slot 0, 1/2 |x_new - x0|^2 in slot ``F``."""
 
@@ -1437,6 +1441,113 @@ class HuberChambollePock(_ExtrapolatedCP):
         """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
         calls; the state of the loop is not touched (halo buffers of its own, one all-reduce of three scalars).  primal = 1/2 |x - x0|^2 +
         reg * sum h_alpha(|D x|_2).  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._gap_certificate(self.x, self.q, 1.0)
+    duality_gap.__doc__ += _GAP_DOC
+
+    def run_until(self, rel_gap, max_iter, check_every=10):
+        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
+        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
+        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
+        """
+        return self._run_until_gap(rel_gap, max_iter, check_every)
+    run_until.__doc__ += _GAP_DOC
+
+
+# =================================================================================================
+class AdaptiveTVChambollePock(AcceleratedChambollePock):
+    """min_x 1/2 |x - x0|^2 + regularization * sum_i g_i |D x|_{2,i} with a PER-VOXEL REGULARISATION WEIGHT g_i >= 0 (``reg_weights``, an
+    array like x0) -- spatially adaptive TV, with the accelerated iteration of ``AcceleratedChambollePock`` (Chambolle & Pock 2011,
+    Algorithm 2: the fidelity is still 1-strongly convex).  What g is for:
+
+        noise-adaptive lambda     CT slices and frames whose noise level varies with dose or path length: g_i follows the local noise
+        edge-stopping weights     g = 1 / (1 + (|D x0|_2 / kappa)^2), the weighted TV of the segmentation and edge-preserving denoising
+                                  literature (``pytv.edge_stopping_weights``)
+        protected regions         g = 0 inside a region of interest: it is left alone while the background is smoothed
+
+    The conjugate of the regulariser differs from plain TV's only in the radius of the ball each site's dual vector is projected onto:
+    regularization * g_i instead of regularization.  D, D^T, the step bound and the schedule are those of plain TV.  Iteration k:
+
+        v      = q + sigma_k D x_bar;  r_i = reg g_i
+        q     <- v where |v|_2 <= r_i, v r_i / |v|_2 beyond                          tv_cp_dual_wtv on x_bar      (2 Nd + 2 words per voxel)
+        x_new <- (x - tau_k D^T q + tau_k x0) / (1 + tau_k)
+        x_bar <- x_new + theta_k (x_new - x);  x <- x_new                           tv_cp_primal_accel, one pass (Nd + 4)
+
+    -- the kernel pair of ``AcceleratedChambollePock`` with another dual epilogue that reads one more array (g): 3 Nd + 6 words per voxel.
+    A site inside its ball keeps v bit for bit and a site with g_i = 0 keeps q = 0 exactly, so a protected voxel whose neighbouring sites
+    are protected too never moves.  All-zero g is allowed: the solver then returns x0.  g is stored like x0 (this
+    rank's planes, pitched with it) and needs no halo plane.  Sharded (``slab``): as ``AcceleratedChambollePock``.
+
+    The model has an EXACT duality gap (tv_dual_gap_wtv), so ``duality_gap`` / ``run_until`` certify the iterate as they do for plain TV.
+
+    Not built (out of scope here): the one-sweep / fix-up form of the iteration (``set_fused(True)`` raises, ``fused`` is always False), a
+    persistent small-volume form, hipGraph capture, the placement tuner / arena of ``ChambollePock``, a plane-marching form of the gap
+    kernel, g under the L1 / Huber / KL / weighted data terms of ``RobustChambollePock`` / ``PoissonChambollePock`` /
+    ``WeightedChambollePock`` or with the Huber-TV regulariser of ``HuberChambollePock``, and g in ``ADMM`` / ``SubgradientDescent``.
+
+    Per-step scalars: the slots of ``ChambollePock`` -- sum g_i |D x_bar|_2 in slot 0, 1/2 |x_new - x0|^2 in slot ``F``."""
+
+    def __init__(self, x0, regularization, reg_weights, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
+                 factor_reg_static=0, tau0=None, sigma0=None, gamma=1.0, slab=None, pitch="auto"):
+        """reg_weights: g, a floating-point (or bool) array of x0's shape (this rank's slab), finite and >= 0; kept in the layout of x0.
+        regularization: finite and > 0.  ValueError otherwise; sharded: the check of g is collective, every rank raises.  tau0, sigma0,
+        gamma, pitch: see ``AcceleratedChambollePock``."""
+        if not (math.isfinite(float(regularization)) and float(regularization) > 0.0):
+            raise ValueError("AdaptiveTVChambollePock: regularization must be finite and > 0")
+        # g is checked BEFORE the state is allocated (an x0 that is no device tensor is left to the base's own refusal)
+        g = self._checked_weights(x0, reg_weights, slab) if isinstance(x0, torch.Tensor) and x0.is_cuda else None
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, tau0, sigma0, gamma, slab, pitch)
+        self.g = self.image_copy(g)
+
+    @staticmethod
+    def _checked_weights(x0, reg_weights, slab):
+        """``reg_weights`` as a device tensor of x0's dtype, or ValueError; ``slab`` (or None) carries the one all-reduce that makes the
+        refusal collective"""
+        g = torch.as_tensor(reg_weights, device=x0.device)
+        shape_ok = tuple(g.shape) == tuple(x0.shape) and (g.dtype == torch.bool or g.dtype.is_floating_point)
+        if shape_ok:
+            g = g.to(x0.dtype)
+            glo, ghi = torch.aminmax(g)                                     # NaN propagates through both
+            bad = (~((glo >= 0) & torch.isfinite(ghi))).to(torch.float64).reshape(1)
+        else:
+            bad = torch.ones(1, dtype=torch.float64, device=x0.device)
+        if slab is not None:
+            slab.allreduce_sum_(bad)
+        if not shape_ok:
+            raise ValueError("AdaptiveTVChambollePock: reg_weights must be a bool or floating-point array of x0's shape, %r (got %r, %s)"
+                             % (tuple(x0.shape), tuple(g.shape), g.dtype))
+        if float(bad.item()) != 0.0:
+            raise ValueError("AdaptiveTVChambollePock: reg_weights must be finite and >= 0 everywhere")
+        return g
+
+    def set_fused(self, fused):
+        """The one-sweep kernels do not know about g: True raises ValueError; False and None (the construction default) keep the kernel
+        pair.  ``fused`` is always False."""
+        if fused:
+            raise ValueError("set_fused(True): AdaptiveTVChambollePock has no one-sweep path (the one-sweep kernels take a scalar lambda)")
+        self._fused = False
+
+    def _dual_kernel(self, sigma, out_ptr):
+        _nv.check(self.lib.tv_cp_dual_wtv(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
+                                          _nv.ptr(self.g), sigma, self.reg, out_ptr, _nv.ptr(self.ws), self.stream))
+
+    _GAP_DOC = """For P(x) = 1/2 |x - x0|^2 + reg sum g_i |D x|_{2,i} and any dual variable q with |q|_2 <= reg g_i per site,
+        Dual(q) = <D^T q, x0> - 1/2 |D^T q|^2 <= P(x*) <= P(x), and by strong convexity 1/2 |x - x*|^2 <= P(x) - Dual(q).  The kernel
+        (tv_dual_gap_wtv) sums the gap site by site as 1/2 (x - x0 + D^T q)^2 + (reg g_i |D x|_2 - <q, D x>), both parts >= 0, and writes
+        nothing but three scalars.
+        fp32 FLOOR: the cancellation inside the second part leaves an absolute error of order eps_fp32 * P, so relative gaps below about
+        1e-6 are not resolvable in fp32; the gap may then come out slightly negative (it is not clamped) and ``run_until`` ends on its
+        iteration limit with ``converged=False``."""
+
+    def _gap_kernel(self, x, q, qscale, b, out):
+        _nv.check(self.lib.tv_dual_gap_wtv(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]),
+                                           _nv.ptr(b["qn"]), _nv.ptr(self.x0), _nv.ptr(self.g), self.reg, out.data_ptr(), _nv.ptr(self.ws),
+                                           self.stream))
+
+    def duality_gap(self):
+        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+        calls; the state of the loop is not touched.  primal = 1/2 |x - x0|^2 + reg * sum g_i |D x|_2.  Sharded: collective, every rank
+        calls it and gets the same numbers.
         """
         return self._gap_certificate(self.x, self.q, 1.0)
     duality_gap.__doc__ += _GAP_DOC
@@ -1733,7 +1844,7 @@ class WeightedChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
     w > 0, and with gamma = min w the schedule of Algorithm 2 did not beat the fixed steps reliably in a NumPy restatement, so this solver
     runs Algorithm 1 only --, a one-sweep / fix-up form of the iteration, hipGraph capture, a persistent small-volume form, the placement
     tuner / arena of ``ChambollePock``, an ``x_init`` argument, and per-voxel weights on the TV term (``mask_static`` weights its time
-    component only).
+    component only) under this data term: ``AdaptiveTVChambollePock`` has them for the plain quadratic data term.
 
     Per-step scalars: the slots of ``ChambollePock`` -- |D x_bar|_{2,1} in slot 0, 1/2 sum w (x_new - x0)^2 in slot ``F``."""
 

@@ -439,6 +439,22 @@ int tv_cp_accel_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_pr
                       int64_t chunk_begin, int64_t chunk_count, double* tv, double* fid, void* ws, void* stream);
 int tv_cp_accel_fixup(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, void* xbar_out, const void* x0,
                       double tau, double theta, int64_t z_begin, int64_t z_count, double* fid, void* ws, void* stream);
+/* One-sweep form of the HUBER-TV iteration (tv_cp_dual_huber on x_bar + tv_cp_primal_accel with constant tau and theta; same geometries as
+ * tv_cp_fused: tv_cp_fused_supported).  tv_cp_accel_sweep with the Huber dual update -- per channel one more multiply, then the same projection:
+ *   tv_cp_huber_sweep : v = (q_in + sigma_D D xbar_in) / (1 + sigma_D alpha / lambda);  q_out <- v / max(1, |v|_2 / lambda);
+ *                       x_new, xbar_out, x exactly as tv_cp_accel_sweep, EXCEPT the adjoint terms tv_cp_fused leaves out;
+ *                       *hub = sum_sites h_alpha(|D xbar_in|_2) over the local planes, each site as (n - a) + a^2 / (2 alpha), a = min(n, alpha), in
+ *                       fp64 (tv_cp_dual_huber's sum);  *fid and the flags TV_CP_FID_OF_INPUT / TV_CP_FID_BOTH as tv_cp_accel_sweep
+ * 1 / (1 + sigma_D alpha / lambda) and 1 / (2 alpha) are formed once in double.  2 Nd + 5 words per voxel where the pair tv_cp_dual_huber +
+ * tv_cp_primal_accel moves 3 Nd + 5.
+ * THE FIX-UP OF THIS SWEEP IS tv_cp_accel_fixup, called with the same tau and theta (and q_out): it only gathers D^T q terms from the stored
+ * dual variable, whatever update produced it.  There is no fix-up symbol of its own.
+ * Flags, chunk ranges, halos, aliasing rules, the 16-byte alignment test and the bit-for-bit statements about ranges and slabs are those of
+ * tv_cp_accel_sweep.  TV_E_ARG, each with its own message, before any device access: every case tv_cp_accel_sweep refuses, and alpha not finite
+ * or not > 0 (alpha = 0 is plain TV: tv_cp_accel_sweep).  A missing halo plane is TV_E_HALO. */
+int tv_cp_huber_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
+                      const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double alpha, double tau, double theta,
+                      int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* hub, double* fid, void* ws, void* stream);
 
 /* ---- fused ADMM updates (not in the reference; README.md:26,135 mention only) --------------- */
 /* v = D x + u; z = v * max(0, 1 - thresh/|v|_2); u = v - z; *tv (device fp64) = |D x|_{2,1}. */

@@ -320,7 +320,7 @@ template <typename T> struct FusedArgsT {
     const T* x0;
     T* p;
     T* x_out;
-    T sigma, inv_lambda, tau, sigma_a, inv_1p_sigma_a;      // ALG_CPACC: sigma_a holds theta, inv_1p_sigma_a holds 1 / (1 + tau)
+    T sigma, inv_lambda, tau, sigma_a, inv_1p_sigma_a;      // ALG_CPACC / ALG_CPHUB: sigma_a holds theta, inv_1p_sigma_a holds 1 / (1 + tau)
     double* part_tv;
     double* part_fid;
     int full_store;       // ALG_ADMM: bit 0 = every sample of t' is stored (z stays recoverable; else only what the fix-up reads), bit 1 = the second partial is |x - x0|^2
@@ -331,6 +331,9 @@ template <typename T> struct FusedArgsT {
                           // (tools/archive/bwtest4 variant 4: 5.98 against 5.50 TB/s) -- the price is a second q array
     double* part_fid2;    // ALG_CP, full_store bit 2 (TV_CP_FID_BOTH, round 5): per-block partials of 1/2 |x_out - x0|^2 over the complete sites, NEXT TO the
                           // fidelity of the input -- the last sweep of a lagged block returns both, so that no separate reduction closes the block
+    // ALG_CPHUB only (at the END: the initialisers of the other entry points stop at part_fid2 and leave these zero, nobody reads them there)
+    T shrink;             // 1 / (1 + sigma alpha / lambda), formed in double by the host
+    double alpha, half_inv_alpha;      // the Huber threshold and 1 / (2 alpha) of the partial sum h_alpha(|D x|_2)
 };
 using FusedArgs = FusedArgsT<float>;
 
@@ -352,7 +355,13 @@ using FusedArgs = FusedArgsT<float>;
 //            tv_stencil.h);  x_bar_out = x_new + theta (x_new - x);  x <- x_new in place.  theta travels in sigma_a, 1 / (1 + tau) in
 //            inv_1p_sigma_a.  Partials as ALG_CP with x in the role of the iterate.  x_new and x_bar are both affine in D^T q', so the
 //            fix-up adds the missing terms to BOTH arrays (FixupArgsT::x_out2 / tau2).
-constexpr int ALG_CP = 0, ALG_ADMM = 1, ALG_CPOP = 2, ALG_CPACC = 3;
+//   ALG_CPHUB: the Huber-TV iteration of HuberChambollePock -- ALG_CPACC with constant tau / theta and the dual update of
+//            cp_dual_huber_site (tv_stencil.h): v = shrink (q + sigma D x_bar) per channel, then the same projection; the first partial is
+//            sum h_alpha(|D x_bar|_2) per column as (n - a) + a^2 / (2 alpha), a = min(n, alpha), in fp64.  Everything else -- primal epilogue, partial
+//            slots, prefetches -- is ALG_CPACC's (alg_extrapolates), and its fix-up IS ALG_CPACC's: the fix-up only gathers D^T q' terms from the stored q'.
+constexpr int ALG_CP = 0, ALG_ADMM = 1, ALG_CPOP = 2, ALG_CPACC = 3, ALG_CPHUB = 4;
+// the ALGs with the state (x, x_bar, q) and the extrapolating primal epilogue
+constexpr bool alg_extrapolates(int alg) { return alg == ALG_CPACC || alg == ALG_CPHUB; }
 
 // XW: the CP_NW waves of a block exchange their tile-edge column terms through LDS (one barrier per plane)
 // TWIN: time windows for volumes with more than CP_TWN frames -- grid z = window, the block works on the frames
@@ -465,11 +474,12 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
     // sweep 32.8 -> 31.8 ms on average, best allocation 31.0 -> 30.7; ADMM hybrid 14.11 -> 14.01 ms, upwind 10.66 -> 10.48.  Not for central
     // (its M = 8 instantiations spill 36 - 100 B with it) nor the hybrid single-window instantiations for 6 - 8 frames (12 - 88 B).
     // ALG_CPACC: not for the downwind single-window instantiation of 8 frames either (36 B with it, where its ALG_CP sibling has none:
-    // profiles/cp_accel_sweep_regs.txt).  (The spill figures above are those of the rounds that measured them; the table in that file
+    // profiles/cp_accel_sweep_regs.txt); ALG_CPHUB shares that exclusion and needs none of its own (profiles/huber_cp_sweep_regs.txt: no
+    // instantiation with scratch where its ALG_CPACC sibling has none).  (The spill figures above are those of the rounds that measured them; the table in that file
     // is the kernel as it is now, sumsq_slots_pinned included.)
     constexpr bool PFX = (TV_FUSED_PFX != 0) && XW && sizeof(T) == 4 &&
                          (S == UPWIND || S == DOWNWIND || (S == HYBRID && (TWIN || M <= 5))) &&
-                         !(ALG == ALG_CPACC && S == DOWNWIND && !TWIN && M == 8);
+                         !(alg_extrapolates(ALG) && S == DOWNWIND && !TWIN && M == 8);
     auto finalize = [&](int zf, int t, const VT& xv, VT racc, bool pre = false, const VT& pre0 = VT{}, const VT& pre1 = VT{}) {
         if (!c.ok || t0 + t >= Mg) return;
         const int eb = (zf - c.zs) & 1;
@@ -507,7 +517,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
         const VT x0v = (PFX && pre) ? pre0 : ldu_s_t<T, V>(a.x0 + foff, voff), pv = (PFX && pre) ? pre1 : ldu_s_t<T, V>(a.p + foff, voff);
         VT pn, xo;
         double e2 = 0.0;
-        if constexpr (ALG == ALG_CPACC) {     // pv is the iterate x, xv (x_bar) is not used: pn = x_new (in place), xo = the next x_bar
+        if constexpr (alg_extrapolates(ALG)) {     // pv is the iterate x, xv (x_bar) is not used: pn = x_new (in place), xo = the next x_bar
 #pragma unroll
             for (int i = 0; i < V; ++i) {
                 pn.v[i] = ((pv.v[i] - a.tau * (s * racc.v[i])) + a.tau * x0v.v[i]) * a.inv_1p_sigma_a;
@@ -538,7 +548,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
             // in registers, so the fix-up no longer has to read x0 for the sites it completes -- the solver takes 1/2 |x_k - x0|^2
             // from sweep k (README.md:157 pairs it with the TV of x_{k-1}, which sweep k - 1 delivered).  TV_CP_FID_BOTH (round 5): the
             // fidelity of the OUTPUT over the complete sites goes to the second accumulator as well (the fix-up, called with x0, adds the rest)
-            const VT& xin = (ALG == ALG_CPACC) ? pv : xv;      // the iterate this sweep started from
+            const VT& xin = alg_extrapolates(ALG) ? pv : xv;      // the iterate this sweep started from
             double f2 = 0.0;
 #pragma unroll
             for (int i = 0; i < V; ++i) {
@@ -607,7 +617,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
                 constexpr int NTX = TV_FUSED_NT ? BUF_NT : 0;
                 if constexpr (ALG == ALG_CPOP) fx0 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.p + fo, z > c.zs, fb), bo);
                 else fx0 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.x0 + fo, z > c.zs, fb), bo);
-                if constexpr (ALG == ALG_CP || ALG == ALG_CPACC) fx1 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.p + fo, z > c.zs, fb), bo);
+                if constexpr (ALG == ALG_CP || alg_extrapolates(ALG)) fx1 = buf_ld<T, V, NTX>(buf_rsrc<T>(a.p + fo, z > c.zs, fb), bo);
             }
             VT qcur[PFQ ? 4 : 1];
             if (PFQ) {
@@ -695,7 +705,8 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
                 for_each_channel<S>(g, [&](auto slot, int ch) {
                     constexpr int k = decltype(slot)::value;
                     const VT qv = PFQ ? qcur[k & 3] : ldu_s_t<T, V>(qbase_in + (long long)ch * g.s_z, voff);
-                    v[k] = (ALG == ALG_ADMM) ? o[k] + qv : qv + a.sigma * o[k];
+                    if constexpr (ALG == ALG_CPHUB) v[k] = a.shrink * (qv + a.sigma * o[k]);      // shrink, then project (cp_dual_huber_site)
+                    else v[k] = (ALG == ALG_ADMM) ? o[k] + qv : qv + a.sigma * o[k];
                     vs = vs + v[k] * v[k];
                 });
                 const VT ds = sumsq_slots_pinned<(S == HYBRID) ? 8 : 4, T, V>(o);
@@ -734,7 +745,13 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
                 } else {
 #pragma unroll
                     for (int i = 0; i < V; ++i) {
-                        acc_tv += (double)tsqrt(ds.v[i]);
+                        if constexpr (ALG == ALG_CPHUB) {         // h_alpha(|D x_bar|_2): no branch, fp64
+                            const double n = (double)tsqrt(ds.v[i]);
+                            const double ha = fmin(n, a.alpha);
+                            acc_tv += (n - ha) + ha * ha * a.half_inv_alpha;
+                        } else {
+                            acc_tv += (double)tsqrt(ds.v[i]);
+                        }
                         scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * a.inv_lambda);
                     }
                     for_each_channel<S>(g, [&](auto slot, int ch) {
@@ -831,7 +848,7 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
     if (threadIdx.x == 0 && threadIdx.y == 0) a.part_tv[linear_block_id()] = acc_tv;
     acc_fid = block_sum(acc_fid, sm);
     if (threadIdx.x == 0 && threadIdx.y == 0) a.part_fid[linear_block_id()] = acc_fid;
-    if constexpr (ALG == ALG_CP || ALG == ALG_CPACC) {
+    if constexpr (ALG == ALG_CP || alg_extrapolates(ALG)) {
         if (a.full_store & 4) {               // uniform
             acc_fid2 = block_sum(acc_fid2, sm);
             if (threadIdx.x == 0 && threadIdx.y == 0) a.part_fid2[linear_block_id()] = acc_fid2;

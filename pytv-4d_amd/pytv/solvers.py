@@ -17,7 +17,8 @@ fused HIP kernels (include/pytv4d.h):
                         fidelity, extrapolation)  (Nd+4): TV-KL for photon-counting data
     WeightedChambollePock tv_cp_dual on the extrapolated point + tv_cp_primal_wls (D^T, prox of a per-voxel weighted quadratic fidelity
                         clamped to a box, extrapolation)  (Nd+5): inpainting of unknown voxels, heteroscedastic data, bounds on the iterate
-    HuberChambollePock  tv_cp_dual_huber on the extrapolated point (shrink + projection, Huber partial) + tv_cp_primal_accel with fixed steps:
+    HuberChambollePock  tv_cp_dual_huber on the extrapolated point (shrink + projection, Huber partial) + tv_cp_primal_accel with fixed steps
+                        (or tv_cp_huber_sweep + tv_cp_accel_fixup: one sweep, 5+2Nd words/voxel + fix-up):
                         the Huber-TV regulariser against staircasing, linearly convergent (Chambolle & Pock 2011, Algorithm 3)
     AdaptiveTVChambollePock  tv_cp_dual_wtv on the extrapolated point (projection onto a per-voxel radius reg * g_i, weighted TV partial)
                         (2Nd+2) + tv_cp_primal_accel with the accelerated schedule: spatially adaptive TV (noise-adaptive lambda,
@@ -1374,22 +1375,33 @@ class HuberChambollePock(_ExtrapolatedCP):
     -- the kernel pair of ``AcceleratedChambollePock`` with another dual epilogue: 3 Nd + 5 words per voxel.  Sharded (``slab``): the boundary
     plane(s) of x_bar travel before the dual kernel and those of q before the primal kernel, both waits exposed.
 
+    The ONE-SWEEP path (``set_fused``, ``fused``) runs the same iteration as tv_cp_huber_sweep +
+    tv_cp_accel_fixup -- the one-sweep kernel of ``AcceleratedChambollePock`` with one more multiply per channel in its dual update and the
+    Huber sum as its first partial; the fix-up is that solver's, unchanged.  x_bar is ping-ponged with a second buffer, x is updated in
+    place, q is read and written once: 2 Nd + 5 words per voxel.  The state (x, x_bar, q) is the same on both paths, so ``set_fused`` may be
+    called between iterations at any time.  DEFAULT: ``ChambollePock``'s rule -- the sweep where tv_cp_fused_supported accepts the geometry,
+    the volume is not sharded and holds at least 1024 * TV_FUSED_MIN_KVOXELS (16 Mi) voxels, the pair otherwise.  Measured on
+    64x8x1024x1024 fp32 (profiles/huber_cp_sweep_bench.txt): the sweep path takes 0.66 - 0.83 of the pair's time per
+    iteration in all four schemes and 1.00 - 1.03 of ``AcceleratedChambollePock``'s one-sweep iteration, so the rule holds for every scheme.
+
     The model has an EXACT duality gap (``duality_gap``, ``run_until``), as the plain-TV solvers have.
 
     alpha -> 0 makes mu -> 0 (tau -> 0, sigma -> inf): the linear rate degenerates, and ``AcceleratedChambollePock`` -- plain TV, O(1/k^2)
     -- is then the solver to use.  alpha = 0 is refused.
 
-    Not built (out of scope here): a one-sweep / fix-up form of this iteration, a persistent small-volume form, hipGraph capture, the
-    placement tuner / arena of ``ChambollePock``, a plane-marching form of the gap kernel, and Huber-TV under the L1 / Huber / KL data terms
-    of ``RobustChambollePock`` / ``PoissonChambollePock``.  A per-voxel weight on the (plain) TV term is ``AdaptiveTVChambollePock``.
+    Not built (out of scope here): the sweep / exchange / fix-up schedule of a sharded slab on the one-sweep path (slabs run the kernel
+    pair), a persistent small-volume form, hipGraph capture, the placement tuner / arena of ``ChambollePock``, a plane-marching form of the
+    gap kernel, and Huber-TV under the L1 / Huber / KL data terms of ``RobustChambollePock`` / ``PoissonChambollePock``.  A per-voxel
+    weight on the (plain) TV term is ``AdaptiveTVChambollePock``.
 
-    Per-step scalars: the slots of ``ChambollePock`` -- sum h_alpha(|D x_bar|_2) in slot 0, 1/2 |x_new - x0|^2 in slot ``F``."""
+    Per-step scalars: the slots of ``ChambollePock`` -- sum h_alpha(|D x_bar|_2) in slot 0, 1/2 |x_new - x0|^2 in slot ``F`` (one-sweep
+    path: the sweep's part in slot ``F``, the fix-up's in ``F + 1``; they are summed when the loss is asked for)."""
 
     def __init__(self, x0, regularization, alpha, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
                  factor_reg_static=0, gamma=1.0, slab=None, pitch="auto"):
         """alpha: see the class docstring; finite and > 0, as is ``regularization``.  gamma: the strong-convexity constant of the fidelity the
         steps are computed for, 0 < gamma <= 1 (1.0 = its true value; smaller = more conservative steps).  ValueError otherwise.  pitch: see
-        ``_SlabProblem``."""
+        ``_SlabProblem``.  The path of the iterations starts at the default rule of the class docstring; ``set_fused`` changes it."""
         alpha, gamma = float(alpha), float(gamma)
         if not (math.isfinite(alpha) and alpha > 0.0):
             raise ValueError("HuberChambollePock: alpha must be finite and > 0 (alpha = 0 is plain TV: AcceleratedChambollePock)")
@@ -1401,6 +1413,29 @@ class HuberChambollePock(_ExtrapolatedCP):
         self.alpha, self.gamma = alpha, gamma
         self.tau, self.sigma, self.theta, self.mu = cp_linear_steps(self.L2, gamma, alpha / self.reg)
         self._alloc_state()
+        self.x_bar_alt = None            # ping-pong partner of x_bar on the one-sweep path, allocated on first use
+        self.set_fused(None)
+
+    @property
+    def fused(self):
+        """True: iterations run as tv_cp_huber_sweep + tv_cp_accel_fixup; False: as tv_cp_dual_huber + tv_cp_primal_accel (``set_fused``)"""
+        return self._fused
+
+    def set_fused(self, fused):
+        """Choose the path of the iterations that follow.  True = the one-sweep kernel (ValueError where tv_cp_fused_supported refuses the
+        geometry, and on a sharded slab: the sweep / exchange / fix-up schedule of slabs is not built for this solver), False = the kernel
+        pair, None = the construction default (class docstring).  The state is untouched; ``reset()`` keeps the choice."""
+        supported = bool(self.lib.tv_cp_fused_supported(self.geo.ref))
+        if fused is None:
+            # ``ChambollePock``'s rule: supported, unsharded, enough voxels to fill the GPU with the sweep's blocks (TV_FUSED_MIN_KVOXELS)
+            fused = supported and not self.slab.sharded and self.x0.numel() >= 1024 * _nv.get_option("TV_FUSED_MIN_KVOXELS", 16384)
+        elif fused:
+            if not supported:
+                raise ValueError("the one-sweep kernel does not support this geometry (tv_cp_fused_supported: whole 16-byte lanes or pitched "
+                                 "rows, Nx >= 64, frames below 2^31 bytes)")
+            if self.slab.sharded:
+                raise ValueError("set_fused(True): the one-sweep path of HuberChambollePock takes unsharded volumes only")
+        self._fused = bool(fused)
 
     def _dual_kernel(self, sigma, out_ptr):
         _nv.check(self.lib.tv_cp_dual_huber(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
@@ -1411,6 +1446,19 @@ class HuberChambollePock(_ExtrapolatedCP):
         slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch."""
         out = self._scratch if out is None else out
         F = self.F
+        if self._fused:
+            # one sweep over all chunks (x_bar -> x_bar_alt, x and q in place), one fix-up over all planes; both return a part of the fidelity
+            if self.x_bar_alt is None:
+                self.x_bar_alt = self.new_image()
+            g, ws, st = self.geo.ref, _nv.ptr(self.ws), self.stream
+            _nv.check(self.lib.tv_cp_huber_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
+                                                 _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), self.sigma, self.reg, self.alpha, self.tau,
+                                                 self.theta, 0, 0, -1, out[0:1].data_ptr(), out[F:F + 1].data_ptr(), ws, st))
+            _nv.check(self.lib.tv_cp_accel_fixup(g, _nv.ptr(self.q), None, None, _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), _nv.ptr(self.x0),
+                                                 self.tau, self.theta, 0, -1, out[F + 1:F + 2].data_ptr(), ws, st))
+            self.x_bar, self.x_bar_alt = self.x_bar_alt, self.x_bar
+            self.it += 1
+            return
         self._dual_half(self.sigma, out)
         _nv.check(self.lib.tv_cp_primal_accel(self.geo.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x),
                                               _nv.ptr(self.x_bar), _nv.ptr(self.x0), self.tau, self.theta, out[F:F + 1].data_ptr(),

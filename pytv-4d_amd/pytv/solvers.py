@@ -35,6 +35,7 @@ fp64 and are all-reduced there; nothing synchronises with the host inside the lo
 """
 
 import math
+import types
 
 import torch
 
@@ -196,6 +197,15 @@ def _plane0(halo):
     return halo[0] if halo is not None else None
 
 
+def _redoc(fn, head=None, tail=""):
+    """The method ``fn`` again -- the same code object, signature and defaults, no call in between -- under the docstring ``head``
+    (None: its own) + ``tail``.  How a class states its own text (its model's ``_GAP_DOC`` / ``_RES_DOC``, what its scalars mean) for a
+    method whose one body lives in a base class."""
+    f = types.FunctionType(fn.__code__, fn.__globals__, fn.__name__, fn.__defaults__, fn.__closure__)
+    f.__qualname__, f.__doc__ = fn.__qualname__, (fn.__doc__ if head is None else head) + tail
+    return f
+
+
 class _SlabProblem:
     """Common state: local slab geometry (and sub-slab geometries for interior / edge launches)."""
 
@@ -251,6 +261,18 @@ class _SlabProblem:
             geo = None
         self.geo = geo if geo is not None else self.geom(0, nz)
         self._geoms[(0, nz)] = self.geo
+
+    def _one_sweep_default(self, sharded_ok):
+        """The default-path rule of the Chambolle-Pock solvers: the one-sweep kernel where tv_cp_fused_supported accepts the geometry --
+        except on volumes too small to fill the GPU with its blocks (8 rows x 256 columns x >= 8 planes x all frames each: a block holds
+        >= 16 k x M voxels and a CU takes 8 / M of them, so 256 CUs want >= 33 Mvoxel for one full round; tools/archive/fused_vs_pair.py:
+        0.5 - 0.7 x of the kernel pair at 6 - 8 Mvoxel with few planes, break-even at 8 - 13 Mvoxel, 1.15 - 1.25 x faster from 16 Mvoxel on
+        whatever the plane size -- 256x1x512x512 runs 990 - 1040 it/s against 870).  Option TV_FUSED_MIN_KVOXELS (thousands of voxels of
+        this rank's slab) moves the switch.  sharded_ok: False = never on a sharded slab (the solvers whose one-sweep path has no
+        sweep / exchange / fix-up schedule)."""
+        if self.slab.sharded and not sharded_ok:
+            return False
+        return bool(self.lib.tv_cp_fused_supported(self.geo.ref)) and self.x0.numel() >= 1024 * _nv.get_option("TV_FUSED_MIN_KVOXELS", 16384)
 
     # ---- persistent small-volume loops (round 6; csrc/tv_small.hip) ------------------------------------------------------------------
     SMALL_MAX_VOXELS = 4 << 20      # the automatic rule: volumes of at most 4 Mvoxel take it (the reference's own shapes hold 0.07 - 1; measured against
@@ -632,8 +654,28 @@ class _SlabProblem:
             self.placement = {"error": str(exc)[:200]}
 
 
+class _GapStopping:
+    """``duality_gap`` / ``run_until`` of the solvers whose state (x, q) carries an exact duality gap (``ChambollePock``,
+    ``AcceleratedChambollePock``, ``HuberChambollePock``, ``AdaptiveTVChambollePock``), over ``_gap_certificate`` / ``_run_until_gap`` of
+    ``_SlabProblem``.  A class binds the two under its own text with ``_redoc``: the ``_GAP_DOC`` of its model as the tail (a head of its
+    own where it says more) and supplies ``_gap_kernel`` where its gap is not plain TV's."""
+
+    def duality_gap(self):
+        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+        calls; the state of the loop is not touched.  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._gap_certificate(self.x, self.q, 1.0)
+
+    def run_until(self, rel_gap, max_iter, check_every=10):
+        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
+        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
+        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
+        """
+        return self._run_until_gap(rel_gap, max_iter, check_every)
+
+
 # =================================================================================================
-class ChambollePock(_SlabProblem):
+class ChambollePock(_GapStopping, _SlabProblem):
     """min_x 1/2 |x - x0|^2 + regularization * TV(x), README.md:141-157 with the state on the GPU.
 
     Per-step scalars: ``SLOTS`` fp64 device words, TV parts in [0:7], fidelity parts in [7:14] (one slot per
@@ -677,14 +719,7 @@ class ChambollePock(_SlabProblem):
         if fused is None and persistent is True:
             fused = False                                 # the persistent loop was asked for: it replaces the kernel pair, not the one-sweep kernel
         if fused is None:
-            # one-sweep kernel where supported -- except on volumes too small to fill the GPU with its blocks (8 rows x 256
-            # columns x >= 8 planes x all frames each: a block holds >= 16 k x M voxels and a CU takes 8 / M of them, so
-            # 256 CUs want >= 33 Mvoxel for one full round; tools/archive/fused_vs_pair.py: 0.5 - 0.7 x of the kernel pair at
-            # 6 - 8 Mvoxel with few planes, break-even at 8 - 13 Mvoxel, 1.15 - 1.25 x faster from 16 Mvoxel on whatever
-            # the plane size -- 256x1x512x512 runs 990 - 1040 it/s against 870).  Option TV_FUSED_MIN_KVOXELS (thousands of
-            # voxels of this rank's slab) moves the switch.
-            min_vox = 1024 * _nv.get_option("TV_FUSED_MIN_KVOXELS", 16384)
-            fused = bool(self.lib.tv_cp_fused_supported(self.geo.ref)) and self.x0.numel() >= min_vox
+            fused = self._one_sweep_default(sharded_ok=True)      # (this solver has the slab schedule of the one-sweep path)
         # (an explicit fused=False asks for the kernel pair: the persistent loop replaces it only when it is asked for as well)
         if bool(fused) and persistent is True:
             raise ValueError("fused=True and persistent=True are two different kernels: ask for one")
@@ -1135,21 +1170,11 @@ class ChambollePock(_SlabProblem):
 
         self._small_blocks(rows, launch)
 
-    def duality_gap(self):
-        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats -- on every path (kernel pair, one-sweep,
+    duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats -- on every path (kernel pair, one-sweep,
         persistent), between ``run`` / ``run_steps`` calls; the state of the loop is not touched.  Sharded: collective, every rank calls it
         and gets the same numbers.
-        """
-        return self._gap_certificate(self.x, self.q, 1.0)
-    duality_gap.__doc__ += _SlabProblem._GAP_DOC
-
-    def run_until(self, rel_gap, max_iter, check_every=10):
-        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
-        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
-        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
-        """
-        return self._run_until_gap(rel_gap, max_iter, check_every)
-    run_until.__doc__ += _SlabProblem._GAP_DOC
+        """, _SlabProblem._GAP_DOC)
+    run_until = _redoc(_GapStopping.run_until, tail=_SlabProblem._GAP_DOC)
 
     _ROLES = ("it", "x", "x_alt", "q", "q_alt")
 
@@ -1161,14 +1186,24 @@ class ChambollePock(_SlabProblem):
 
 # =================================================================================================
 class _ExtrapolatedCP(_SlabProblem):
-    """What the Chambolle-Pock solvers with the state (x, x_bar, q) share (``AcceleratedChambollePock``, ``RobustChambollePock``,
-    ``PoissonChambollePock``, ``WeightedChambollePock``): the state
-    and its halo planes, the dual half of an iteration -- tv_cp_dual on the extrapolated point x_bar -- and the loop around ``step``.  A
-    subclass validates its steps (``cp_step_pair`` on ``L2``), calls ``_alloc_state`` and supplies ``step``: ``_dual_half`` + its primal
-    kernel.  Per-step scalars: the slots of ``ChambollePock``."""
+    """What the Chambolle-Pock solvers with the state (x, x_bar, q) share (``AcceleratedChambollePock``, ``HuberChambollePock``,
+    ``AdaptiveTVChambollePock``, ``RobustChambollePock``, ``PoissonChambollePock``, ``WeightedChambollePock``): the state and its halo
+    planes, the iteration -- ``step``: a dual kernel on the extrapolated point x_bar, then a primal kernel that extrapolates -- and the
+    loop around it.  A subclass validates its steps (``cp_step_pair`` / ``cp_linear_steps`` on ``L2``), calls ``_alloc_state`` and says
+    what differs through three hooks:
+
+        _steps(k)                           (tau, sigma, theta) of iteration k as Python floats.  Here: the constants ``self.tau``,
+                                            ``self.sigma``, ``self.theta`` (Algorithm 1: theta = 1; Algorithm 3: ``cp_linear_steps``);
+                                            ``AcceleratedChambollePock``: the schedule of Algorithm 2
+        _dual_kernel(sigma, out_ptr)        here tv_cp_dual (plain TV); tv_cp_dual_huber, tv_cp_dual_wtv
+        _primal_kernel(tau, theta, out_ptr) here tv_cp_primal_accel (quadratic fidelity); ``_FixedPointResiduals``: the class's ``_prox``
+
+    and keeps ``step`` / ``run`` under docstrings of its own (what its scalars mean).  The one-sweep form of the iteration is
+    ``_OneSweepCP``.  Per-step scalars: the slots of ``ChambollePock``."""
 
     SLOTS, F = ChambollePock.SLOTS, ChambollePock.F
     loss_from_slots = ChambollePock.loss_from_slots
+    _fused = False          # the kernel pair; ``_OneSweepCP`` makes it a choice
 
     def __init__(self, x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch):
         super().__init__(x0, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch=pitch)
@@ -1193,6 +1228,23 @@ class _ExtrapolatedCP(_SlabProblem):
         self.q.zero_()
         self.it = 0
 
+    def step(self, out=None):
+        """Enqueue one iteration with the steps of iteration ``self.it``.  out: fp64 device tensor of SLOTS words (zero on entry) receiving
+        this rank's regulariser of x_bar in slot 0 and its fidelity of x_new in slot F; defaults to an internal scratch."""
+        out = self._scratch if out is None else out
+        tau, sigma, theta = self._steps(self.it)
+        if self._fused:
+            self._one_sweep(tau, sigma, theta, out)
+        else:
+            F = self.F
+            self._dual_half(sigma, out)
+            self._primal_kernel(tau, theta, out[F:F + 1].data_ptr())
+        self.it += 1
+
+    def _steps(self, k):
+        """(tau_k, sigma_k, theta_k) as Python floats: constant steps"""
+        return self.tau, self.sigma, self.theta
+
     def _dual_half(self, sigma, out):
         """q <- proj_{|.|_2 <= reg}(q + sigma D x_bar), this rank's |D x_bar|_{2,1} into out[0]; sharded: the boundary planes of x_bar travel
         before the kernel and those of the new q after it (into ``qh_prev`` / ``qh_next``, for the primal kernel), both waits exposed."""
@@ -1204,9 +1256,14 @@ class _ExtrapolatedCP(_SlabProblem):
             s.wait(pl.exchange_grad(self.q, _plane0(self.qh_prev), _plane0(self.qh_next)))
 
     def _dual_kernel(self, sigma, out_ptr):
-        """the dual entry point of ``_dual_half``: tv_cp_dual (plain TV); ``HuberChambollePock`` has its own"""
+        """the dual entry point of ``_dual_half``: tv_cp_dual (plain TV); ``HuberChambollePock`` and ``AdaptiveTVChambollePock`` have their own"""
         _nv.check(self.lib.tv_cp_dual(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
                                       sigma, self.reg, out_ptr, _nv.ptr(self.ws), self.stream))
+
+    def _primal_kernel(self, tau, theta, out_ptr):
+        """the primal entry point of ``step``: tv_cp_primal_accel (D^T, the closed-form prox of the quadratic fidelity, extrapolation by theta)"""
+        _nv.check(self.lib.tv_cp_primal_accel(self.geo.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x),
+                                              _nv.ptr(self.x_bar), _nv.ptr(self.x0), tau, theta, out_ptr, _nv.ptr(self.ws), self.stream))
 
     def run_steps(self, rows):
         """Enqueue ``len(rows)`` iterations, row k of the (n, SLOTS) fp64 device tensor ``rows`` (zero on entry) receiving the scalars of
@@ -1224,8 +1281,55 @@ class _ExtrapolatedCP(_SlabProblem):
         return self.loss_from_slots(hist.cpu().numpy(), self.reg)
 
 
+class _OneSweepCP(_ExtrapolatedCP):
+    """The one-sweep path of an ``_ExtrapolatedCP`` solver with the quadratic fidelity (``AcceleratedChambollePock``, ``HuberChambollePock``):
+    a sweep kernel -- x_bar is its stencil input and is ping-ponged with a second buffer, x and q are updated in place -- followed by
+    tv_cp_accel_fixup.  The state (x, x_bar, q) is that of the kernel pair.  A class supplies ``_sweep_kernel(tau, sigma, theta, tv_ptr,
+    fid_ptr, g, ws, st)`` (one launch over all chunks, x_bar -> x_bar_alt; g, ws, st: the geometry reference, workspace pointer and stream
+    that the two launches of an iteration share), ends its constructor with ``_init_path()`` and binds ``fused`` / ``step`` under its
+    own text."""
+
+    def _init_path(self):
+        """the end of construction: no partner of x_bar yet, the default path"""
+        self.x_bar_alt = None            # ping-pong partner of x_bar on the one-sweep path, allocated on first use
+        self.set_fused(None)
+
+    @property
+    def fused(self):
+        """True: iterations run as the sweep kernel + tv_cp_accel_fixup; False: as the kernel pair (``set_fused``)"""
+        return self._fused
+
+    def set_fused(self, fused):
+        """Choose the path of the iterations that follow.  True = the one-sweep kernel (ValueError where tv_cp_fused_supported refuses the
+        geometry, and on a sharded slab: the sweep / exchange / fix-up schedule of slabs is not built for this solver), False = the kernel
+        pair, None = the construction default (class docstring).  The state is untouched; ``reset()`` keeps the choice."""
+        if fused is None:
+            fused = self._one_sweep_default(sharded_ok=False)        # ``ChambollePock``'s rule, unsharded volumes only
+        elif fused:
+            if not self.lib.tv_cp_fused_supported(self.geo.ref):
+                raise ValueError("the one-sweep kernel does not support this geometry (tv_cp_fused_supported: whole 16-byte lanes or pitched "
+                                 "rows, Nx >= 64, frames below 2^31 bytes)")
+            if self.slab.sharded:
+                raise ValueError("set_fused(True): the one-sweep path of %s takes unsharded volumes only" % type(self).__name__)
+        self._fused = bool(fused)
+
+    def _one_sweep(self, tau, sigma, theta, out):
+        """the iteration as one sweep over all chunks (x_bar -> x_bar_alt, x and q in place) and one fix-up over all planes; both return a
+        part of the fidelity (slots F, F + 1)"""
+        if self.x_bar_alt is None:
+            # (lazy, and so AFTER the state arrays: where separate allocations land moves the streaming kernels' time, ``_alloc_state``)
+            self.x_bar_alt = self.new_image()
+        F = self.F
+        # (fetched once for both launches: fetching them again for the fix-up measured 1 - 2 us on a 30 us launch-bound iteration)
+        g, ws, st = self.geo.ref, _nv.ptr(self.ws), self.stream
+        self._sweep_kernel(tau, sigma, theta, out[0:1].data_ptr(), out[F:F + 1].data_ptr(), g, ws, st)
+        _nv.check(self.lib.tv_cp_accel_fixup(g, _nv.ptr(self.q), None, None, _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), _nv.ptr(self.x0),
+                                             tau, theta, 0, -1, out[F + 1:F + 2].data_ptr(), ws, st))
+        self.x_bar, self.x_bar_alt = self.x_bar_alt, self.x_bar
+
+
 # =================================================================================================
-class AcceleratedChambollePock(_ExtrapolatedCP):
+class AcceleratedChambollePock(_GapStopping, _OneSweepCP):
     """min_x 1/2 |x - x0|^2 + regularization * TV(x) with the ACCELERATED primal-dual iteration (Chambolle & Pock 2011, Algorithm 2).
     The fidelity is 1-strongly convex: with theta_k = 1 / sqrt(1 + 2 gamma tau_k), tau_{k+1} = theta_k tau_k, sigma_{k+1} = sigma_k / theta_k
     (``accel_schedule``; gamma <= 1) the iterates converge as O(1/k^2) where ``ChambollePock`` -- the reference's README loop, fixed steps,
@@ -1271,29 +1375,10 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
         self.tau0, self.sigma0 = cp_step_pair(self.L2, tau0, sigma0, names=("tau0", "sigma0"))
         self._alloc_state()
         self._sched = None
-        self.x_bar_alt = None            # ping-pong partner of x_bar on the one-sweep path, allocated on first use
-        self.set_fused(None)
+        self._init_path()
 
-    @property
-    def fused(self):
-        """True: iterations run as tv_cp_accel_sweep + tv_cp_accel_fixup; False: as tv_cp_dual + tv_cp_primal_accel (``set_fused``)"""
-        return self._fused
-
-    def set_fused(self, fused):
-        """Choose the path of the iterations that follow.  True = the one-sweep kernel (ValueError where tv_cp_fused_supported refuses the
-        geometry, and on a sharded slab: the sweep / exchange / fix-up schedule of slabs is not built for this solver), False = the kernel
-        pair, None = the construction default (class docstring).  The state is untouched; ``reset()`` keeps the choice."""
-        supported = bool(self.lib.tv_cp_fused_supported(self.geo.ref))
-        if fused is None:
-            # ``ChambollePock``'s rule: supported, unsharded, enough voxels to fill the GPU with the sweep's blocks (TV_FUSED_MIN_KVOXELS)
-            fused = supported and not self.slab.sharded and self.x0.numel() >= 1024 * _nv.get_option("TV_FUSED_MIN_KVOXELS", 16384)
-        elif fused:
-            if not supported:
-                raise ValueError("the one-sweep kernel does not support this geometry (tv_cp_fused_supported: whole 16-byte lanes or pitched "
-                                 "rows, Nx >= 64, frames below 2^31 bytes)")
-            if self.slab.sharded:
-                raise ValueError("set_fused(True): the one-sweep path of AcceleratedChambollePock takes unsharded volumes only")
-        self._fused = bool(fused)
+    fused = property(_OneSweepCP.fused.fget, doc="True: iterations run as tv_cp_accel_sweep + tv_cp_accel_fixup; False: as tv_cp_dual + "
+                                                 "tv_cp_primal_accel (``set_fused``)")
 
     def _steps(self, k):
         """(tau_k, sigma_k, theta_k) as Python floats, from a cached ``accel_schedule`` that grows by doubling"""
@@ -1303,30 +1388,13 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
         tau, sigma, theta = self._sched[1]
         return float(tau[k]), float(sigma[k]), float(theta[k])
 
-    def step(self, out=None):
-        """Enqueue one iteration with the steps of iteration ``self.it``.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this
-        rank's |D x_bar|_{2,1} in slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch."""
-        out = self._scratch if out is None else out
-        tau, sigma, theta = self._steps(self.it)
-        F = self.F
-        if self._fused:
-            # one sweep over all chunks (x_bar -> x_bar_alt, x and q in place), one fix-up over all planes; both return a part of the fidelity
-            if self.x_bar_alt is None:
-                self.x_bar_alt = self.new_image()
-            g, ws, st = self.geo.ref, _nv.ptr(self.ws), self.stream
-            _nv.check(self.lib.tv_cp_accel_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
-                                                 _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), sigma, self.reg, tau, theta, 0, 0, -1,
-                                                 out[0:1].data_ptr(), out[F:F + 1].data_ptr(), ws, st))
-            _nv.check(self.lib.tv_cp_accel_fixup(g, _nv.ptr(self.q), None, None, _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), _nv.ptr(self.x0),
-                                                 tau, theta, 0, -1, out[F + 1:F + 2].data_ptr(), ws, st))
-            self.x_bar, self.x_bar_alt = self.x_bar_alt, self.x_bar
-            self.it += 1
-            return
-        self._dual_half(sigma, out)
-        _nv.check(self.lib.tv_cp_primal_accel(self.geo.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x),
-                                              _nv.ptr(self.x_bar), _nv.ptr(self.x0), tau, theta, out[F:F + 1].data_ptr(), _nv.ptr(self.ws),
-                                              self.stream))
-        self.it += 1
+    def _sweep_kernel(self, tau, sigma, theta, tv_ptr, fid_ptr, g, ws, st):
+        _nv.check(self.lib.tv_cp_accel_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
+                                             _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), sigma, self.reg, tau, theta, 0, 0, -1, tv_ptr, fid_ptr,
+                                             ws, st))
+
+    step = _redoc(_ExtrapolatedCP.step, """Enqueue one iteration with the steps of iteration ``self.it``.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this
+        rank's |D x_bar|_{2,1} in slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch.""")
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
@@ -1336,24 +1404,12 @@ class AcceleratedChambollePock(_ExtrapolatedCP):
         ones included; it never raises."""
         return self._run(n_iter, record_loss)
 
-    def duality_gap(self):
-        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
-        calls; the state of the loop is not touched.  Sharded: collective, every rank calls it and gets the same numbers.
-        """
-        return self._gap_certificate(self.x, self.q, 1.0)
-    duality_gap.__doc__ += _SlabProblem._GAP_DOC
-
-    def run_until(self, rel_gap, max_iter, check_every=10):
-        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
-        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
-        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
-        """
-        return self._run_until_gap(rel_gap, max_iter, check_every)
-    run_until.__doc__ += _SlabProblem._GAP_DOC
+    duality_gap = _redoc(_GapStopping.duality_gap, tail=_SlabProblem._GAP_DOC)
+    run_until = _redoc(_GapStopping.run_until, tail=_SlabProblem._GAP_DOC)
 
 
 # =================================================================================================
-class HuberChambollePock(_ExtrapolatedCP):
+class HuberChambollePock(_GapStopping, _OneSweepCP):
     """min_x 1/2 |x - x0|^2 + regularization * sum_sites h_alpha(|D x|_2) -- the HUBER-TV (Huber-ROF) model of Chambolle & Pock 2011, section
     6.2.1, the standard remedy for the staircasing of plain TV (smooth ramps coming back as terraces):
 
@@ -1413,57 +1469,22 @@ class HuberChambollePock(_ExtrapolatedCP):
         self.alpha, self.gamma = alpha, gamma
         self.tau, self.sigma, self.theta, self.mu = cp_linear_steps(self.L2, gamma, alpha / self.reg)
         self._alloc_state()
-        self.x_bar_alt = None            # ping-pong partner of x_bar on the one-sweep path, allocated on first use
-        self.set_fused(None)
+        self._init_path()
 
-    @property
-    def fused(self):
-        """True: iterations run as tv_cp_huber_sweep + tv_cp_accel_fixup; False: as tv_cp_dual_huber + tv_cp_primal_accel (``set_fused``)"""
-        return self._fused
-
-    def set_fused(self, fused):
-        """Choose the path of the iterations that follow.  True = the one-sweep kernel (ValueError where tv_cp_fused_supported refuses the
-        geometry, and on a sharded slab: the sweep / exchange / fix-up schedule of slabs is not built for this solver), False = the kernel
-        pair, None = the construction default (class docstring).  The state is untouched; ``reset()`` keeps the choice."""
-        supported = bool(self.lib.tv_cp_fused_supported(self.geo.ref))
-        if fused is None:
-            # ``ChambollePock``'s rule: supported, unsharded, enough voxels to fill the GPU with the sweep's blocks (TV_FUSED_MIN_KVOXELS)
-            fused = supported and not self.slab.sharded and self.x0.numel() >= 1024 * _nv.get_option("TV_FUSED_MIN_KVOXELS", 16384)
-        elif fused:
-            if not supported:
-                raise ValueError("the one-sweep kernel does not support this geometry (tv_cp_fused_supported: whole 16-byte lanes or pitched "
-                                 "rows, Nx >= 64, frames below 2^31 bytes)")
-            if self.slab.sharded:
-                raise ValueError("set_fused(True): the one-sweep path of HuberChambollePock takes unsharded volumes only")
-        self._fused = bool(fused)
+    fused = property(_OneSweepCP.fused.fget, doc="True: iterations run as tv_cp_huber_sweep + tv_cp_accel_fixup; False: as tv_cp_dual_huber + "
+                                                 "tv_cp_primal_accel (``set_fused``)")
 
     def _dual_kernel(self, sigma, out_ptr):
         _nv.check(self.lib.tv_cp_dual_huber(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
                                             sigma, self.reg, self.alpha, out_ptr, _nv.ptr(self.ws), self.stream))
 
-    def step(self, out=None):
-        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's sum h_alpha(|D x_bar|_2) in
-        slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch."""
-        out = self._scratch if out is None else out
-        F = self.F
-        if self._fused:
-            # one sweep over all chunks (x_bar -> x_bar_alt, x and q in place), one fix-up over all planes; both return a part of the fidelity
-            if self.x_bar_alt is None:
-                self.x_bar_alt = self.new_image()
-            g, ws, st = self.geo.ref, _nv.ptr(self.ws), self.stream
-            _nv.check(self.lib.tv_cp_huber_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
-                                                 _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), self.sigma, self.reg, self.alpha, self.tau,
-                                                 self.theta, 0, 0, -1, out[0:1].data_ptr(), out[F:F + 1].data_ptr(), ws, st))
-            _nv.check(self.lib.tv_cp_accel_fixup(g, _nv.ptr(self.q), None, None, _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), _nv.ptr(self.x0),
-                                                 self.tau, self.theta, 0, -1, out[F + 1:F + 2].data_ptr(), ws, st))
-            self.x_bar, self.x_bar_alt = self.x_bar_alt, self.x_bar
-            self.it += 1
-            return
-        self._dual_half(self.sigma, out)
-        _nv.check(self.lib.tv_cp_primal_accel(self.geo.ref, _nv.ptr(self.q), _nv.ptr(self.qh_prev), _nv.ptr(self.qh_next), _nv.ptr(self.x),
-                                              _nv.ptr(self.x_bar), _nv.ptr(self.x0), self.tau, self.theta, out[F:F + 1].data_ptr(),
-                                              _nv.ptr(self.ws), self.stream))
-        self.it += 1
+    def _sweep_kernel(self, tau, sigma, theta, tv_ptr, fid_ptr, g, ws, st):
+        _nv.check(self.lib.tv_cp_huber_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
+                                             _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), sigma, self.reg, self.alpha, tau, theta, 0, 0, -1,
+                                             tv_ptr, fid_ptr, ws, st))
+
+    step = _redoc(_ExtrapolatedCP.step, """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's sum h_alpha(|D x_bar|_2) in
+        slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch.""")
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
@@ -1485,21 +1506,11 @@ class HuberChambollePock(_ExtrapolatedCP):
                                              _nv.ptr(b["qn"]), _nv.ptr(self.x0), self.reg, self.alpha, out.data_ptr(), _nv.ptr(self.ws),
                                              self.stream))
 
-    def duality_gap(self):
-        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+    duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
         calls; the state of the loop is not touched (halo buffers of its own, one all-reduce of three scalars).  primal = 1/2 |x - x0|^2 +
         reg * sum h_alpha(|D x|_2).  Sharded: collective, every rank calls it and gets the same numbers.
-        """
-        return self._gap_certificate(self.x, self.q, 1.0)
-    duality_gap.__doc__ += _GAP_DOC
-
-    def run_until(self, rel_gap, max_iter, check_every=10):
-        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
-        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
-        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
-        """
-        return self._run_until_gap(rel_gap, max_iter, check_every)
-    run_until.__doc__ += _GAP_DOC
+        """, _GAP_DOC)
+    run_until = _redoc(_GapStopping.run_until, tail=_GAP_DOC)
 
 
 # =================================================================================================
@@ -1592,29 +1603,44 @@ class AdaptiveTVChambollePock(AcceleratedChambollePock):
                                            _nv.ptr(b["qn"]), _nv.ptr(self.x0), _nv.ptr(self.g), self.reg, out.data_ptr(), _nv.ptr(self.ws),
                                            self.stream))
 
-    def duality_gap(self):
-        """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+    duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
         calls; the state of the loop is not touched.  primal = 1/2 |x - x0|^2 + reg * sum g_i |D x|_2.  Sharded: collective, every rank
         calls it and gets the same numbers.
-        """
-        return self._gap_certificate(self.x, self.q, 1.0)
-    duality_gap.__doc__ += _GAP_DOC
-
-    def run_until(self, rel_gap, max_iter, check_every=10):
-        """Iterate until the answer is certified: ``run`` in blocks of ``check_every`` iterations, stopping at the first check where
-        gap <= rel_gap * max(|primal|, tiny), or after ``max_iter`` iterations.  Returns (loss_history, info); info: ``iterations``, ``primal``,
-        ``dual``, ``gap``, ``converged`` and ``error_bound`` = sqrt(2 max(gap, 0)), the bound on |x - x*|_2.
-        """
-        return self._run_until_gap(rel_gap, max_iter, check_every)
-    run_until.__doc__ += _GAP_DOC
+        """, _GAP_DOC)
+    run_until = _redoc(_GapStopping.run_until, tail=_GAP_DOC)
 
 
 # =================================================================================================
 class _FixedPointResiduals:
     """The optimality residual of the solvers whose fidelity has a pointwise prox but no cheap duality gap (``RobustChambollePock``,
     ``PoissonChambollePock``, ``WeightedChambollePock``): tv_cp_dual_residual for the dual block, the class's primal kernel in residual mode for the fidelity block.
-    The class supplies ``_prox(q, qp, qn, x, x_bar, theta, flags, out_ptr)`` (its primal entry point) and ``_fidelity_value()``, calls
-    ``_init_residuals`` at the end of its constructor, and keeps ``residuals`` / ``run_until`` with docstrings of its own."""
+    The class supplies ``_prox(q, qp, qn, x, x_bar, theta, flags, out_ptr)`` (its primal entry point: the loop's ``_primal_kernel`` and,
+    in residual mode, R_x) and ``_fidelity_value()``, takes its steps with ``_fixed_steps`` (Algorithm 1), calls ``_init_residuals`` at the
+    end of its constructor, and binds ``residuals`` / ``run_until`` under its own text with ``_redoc`` (its ``_RES_DOC`` as the tail)."""
+
+    def _fixed_steps(self, tau, sigma):
+        """the constant steps of Algorithm 1: (tau, sigma) validated by ``cp_step_pair`` on ``L2``, theta = 1"""
+        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        self.theta = 1.0
+
+    def _primal_kernel(self, tau, theta, out_ptr):
+        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, theta, 0, out_ptr)
+
+    def residuals(self):
+        """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": F(x - x0)} of the current pair (x, q) as Python floats, between
+        ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the scalars, one host
+        synchronisation.  Sharded: collective, every rank calls it and gets the same numbers.
+        """
+        return self._residual_dict(self._residual_scalars())
+
+    def run_until(self, rel_res, max_iter, check_every=10):
+        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
+        first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the pair the constructor left
+        (x0, q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
+        Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
+        ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 2-word pass and the fidelity reduction.
+        """
+        return self._run_until_residual(rel_res, max_iter, check_every)
 
     def _init_residuals(self):
         """halo buffers of ``residuals`` (its own: the loop's are not touched), and R_0 of the starting pair, enqueued here and read back
@@ -1693,7 +1719,7 @@ class RobustChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
         self.fidelity, self.fid_code = fidelity, _nv.FIDELITIES[fidelity]
         self.delta = float(delta) if fidelity == "huber" else 0.0
-        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        self._fixed_steps(tau, sigma)
         self._alloc_state()
         self._init_residuals()
 
@@ -1701,13 +1727,8 @@ class RobustChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         _nv.check(self.lib.tv_cp_primal_prox(self.geo.ref, _nv.ptr(q), _nv.ptr(qp), _nv.ptr(qn), _nv.ptr(x), _nv.ptr(x_bar), _nv.ptr(self.x0),
                                              self.fid_code, self.delta, self.tau, theta, flags, out_ptr, _nv.ptr(self.ws), self.stream))
 
-    def step(self, out=None):
-        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
-        F(x_new - x0) in slot F; defaults to an internal scratch."""
-        out = self._scratch if out is None else out
-        self._dual_half(self.sigma, out)
-        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[self.F:self.F + 1].data_ptr())
-        self.it += 1
+    step = _redoc(_ExtrapolatedCP.step, """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
+        F(x_new - x0) in slot F; defaults to an internal scratch.""")
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
@@ -1736,23 +1757,8 @@ class RobustChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         a = e.clamp(max=self.delta)
         return (e - a).sum(dtype=torch.float64) + torch.linalg.vector_norm(a, dtype=torch.float64) ** 2 / (2.0 * self.delta)
 
-    def residuals(self):
-        """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": F(x - x0)} of the current pair (x, q) as Python floats, between
-        ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the scalars, one host
-        synchronisation.  Sharded: collective, every rank calls it and gets the same numbers.
-        """
-        return self._residual_dict(self._residual_scalars())
-    residuals.__doc__ += _RES_DOC
-
-    def run_until(self, rel_res, max_iter, check_every=10):
-        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
-        first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the pair the constructor left
-        (x0, q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
-        Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
-        ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 2-word pass and the fidelity reduction.
-        """
-        return self._run_until_residual(rel_res, max_iter, check_every)
-    run_until.__doc__ += _RES_DOC
+    residuals = _redoc(_FixedPointResiduals.residuals, tail=_RES_DOC)
+    run_until = _redoc(_FixedPointResiduals.run_until, tail=_RES_DOC)
 
 
 # =================================================================================================
@@ -1788,7 +1794,7 @@ class PoissonChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         """x0: the counts, >= 0 and finite (ValueError otherwise: one min / max reduction; sharded: collective, every rank raises).  tau,
         sigma: see the class docstring -- tau * sigma * L^2 > 1 + 1e-12 raises ValueError.  pitch: see ``_SlabProblem``."""
         super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
-        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        self._fixed_steps(tau, sigma)
         lo, hi = torch.aminmax(x0)                       # NaN propagates through both
         bad = (~((lo >= 0) & torch.isfinite(hi))).to(torch.float64).reshape(1)
         self.slab.allreduce_sum_(bad)
@@ -1801,13 +1807,8 @@ class PoissonChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         _nv.check(self.lib.tv_cp_primal_kl(self.geo.ref, _nv.ptr(q), _nv.ptr(qp), _nv.ptr(qn), _nv.ptr(x), _nv.ptr(x_bar), _nv.ptr(self.x0),
                                            self.tau, theta, flags, out_ptr, _nv.ptr(self.ws), self.stream))
 
-    def step(self, out=None):
-        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
-        F(x_new) in slot F; defaults to an internal scratch."""
-        out = self._scratch if out is None else out
-        self._dual_half(self.sigma, out)
-        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[self.F:self.F + 1].data_ptr())
-        self.it += 1
+    step = _redoc(_ExtrapolatedCP.step, """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
+        F(x_new) in slot F; defaults to an internal scratch.""")
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
@@ -1839,23 +1840,11 @@ class PoissonChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
             total += (x - c).sum() + torch.xlogy(c, ratio).sum()
         return total
 
-    def residuals(self):
-        """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": F(x)} of the current pair (x, q) as Python floats, between
+    residuals = _redoc(_FixedPointResiduals.residuals, """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": F(x)} of the current pair (x, q) as Python floats, between
         ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the scalars, one host
         synchronisation.  Sharded: collective, every rank calls it and gets the same numbers.
-        """
-        return self._residual_dict(self._residual_scalars())
-    residuals.__doc__ += _RES_DOC
-
-    def run_until(self, rel_res, max_iter, check_every=10):
-        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
-        first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the pair the constructor left
-        (x0, q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
-        Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
-        ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 2-word pass and the fidelity reduction.
-        """
-        return self._run_until_residual(rel_res, max_iter, check_every)
-    run_until.__doc__ += _RES_DOC
+        """, _RES_DOC)
+    run_until = _redoc(_FixedPointResiduals.run_until, tail=_RES_DOC)
 
 
 # =================================================================================================
@@ -1913,7 +1902,7 @@ class WeightedChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
             x0 = x0 - self.shift
         super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
         self.lower, self.upper = lo - self.shift, hi - self.shift
-        self.tau, self.sigma = cp_step_pair(self.L2, tau, sigma)
+        self._fixed_steps(tau, sigma)
         w = torch.as_tensor(weights, device=self.device)
         if tuple(w.shape) != tuple(x0.shape):
             raise ValueError("WeightedChambollePock: weights must have the shape of x0, %r (got %r)" % (tuple(x0.shape), tuple(w.shape)))
@@ -1962,13 +1951,8 @@ class WeightedChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
                                             _nv.ptr(self.w), self.lower, self.upper, self.tau, theta, flags, out_ptr, _nv.ptr(self.ws),
                                             self.stream))
 
-    def step(self, out=None):
-        """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
-        1/2 sum w (x_new - x0)^2 in slot F; defaults to an internal scratch."""
-        out = self._scratch if out is None else out
-        self._dual_half(self.sigma, out)
-        self._prox(self.q, self.qh_prev, self.qh_next, self.x, self.x_bar, 1.0, 0, out[self.F:self.F + 1].data_ptr())
-        self.it += 1
+    step = _redoc(_ExtrapolatedCP.step, """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's |D x_bar|_{2,1} in slot 0 and
+        1/2 sum w (x_new - x0)^2 in slot F; defaults to an internal scratch.""")
 
     def run(self, n_iter, record_loss=True):
         """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
@@ -1991,23 +1975,16 @@ class WeightedChambollePock(_FixedPointResiduals, _ExtrapolatedCP):
         e = torch.sub(self.x, self.x0)
         return 0.5 * e.mul_(e).mul_(self.w).sum(dtype=torch.float64)
 
-    def residuals(self):
-        """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": 1/2 sum w (x - x0)^2} of the current pair (x, q) as Python
+    residuals = _redoc(_FixedPointResiduals.residuals, """{"x": R_x, "q": R_q, "total": R_x + R_q, "tv": |D x|_{2,1}, "fid": 1/2 sum w (x - x0)^2} of the current pair (x, q) as Python
         floats, between ``step`` / ``run`` calls; x, x_bar, q and the loop's halo planes are left as they are.  One all-reduce of the
         scalars, one host synchronisation.  Sharded: collective, every rank calls it and gets the same numbers.
-        """
-        return self._residual_dict(self._residual_scalars())
-    residuals.__doc__ += _RES_DOC
-
-    def run_until(self, rel_res, max_iter, check_every=10):
-        """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
+        """, _RES_DOC)
+    run_until = _redoc(_FixedPointResiduals.run_until, """Iterate until the residual has dropped by the factor asked for: ``run`` in blocks of ``check_every`` iterations, stopping at the
         first check where R_k <= rel_res**2 * R_0, or after ``max_iter`` iterations.  R_0 is the residual of the pair the constructor left
         (clamp(x0), q = 0); R_0 == 0 (a constant image: a saddle point already) returns at once with ``converged=True``.
         Returns (loss_history, info); info: ``iterations``, ``converged``, ``residuals`` (the last ``residuals()`` dict), ``initial`` = R_0 and
         ``relative`` = sqrt(R_k / R_0).  A check costs one Nd + 1-word pass, one Nd + 3-word pass and the fidelity reduction.
-        """
-        return self._run_until_residual(rel_res, max_iter, check_every)
-    run_until.__doc__ += _RES_DOC
+        """, _RES_DOC)
 
 
 # =================================================================================================

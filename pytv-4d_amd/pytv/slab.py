@@ -269,6 +269,10 @@ class HaloPlan:
         if not self.on:
             return []
         nz = x.shape[0]
+        if nz < 2:
+            # x[nz - 2:nz] would be ONE plane for a neighbour that posted a two-plane receive; and plane z0 - 2 of a one-plane rank
+            # belongs to the rank two away, which a nearest-neighbour exchange cannot fetch
+            raise ValueError("two-plane halos need a slab of >= 2 planes: this rank (%d of %d) holds %d" % (self.slab.rank, self.slab.world, nz))
         return self.slab.exchange(send_prev=x[0:2], send_next=x[nz - 2:nz], recv_prev=recv_prev, recv_next=recv_next)
 
     def exchange_grad(self, q, recv_prev, recv_next):

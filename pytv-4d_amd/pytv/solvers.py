@@ -215,6 +215,8 @@ class _SlabProblem:
         (row_pitch, frame_pitch) in elements = every array of the solver's state (x0 is COPIED into such storage) is pitched
         (include/pytv4d.h, tv_geom::row_pitch / frame_pitch).  With padded state ``result()`` / ``x`` are (Nz, M, Ny, Nx) VIEWS of
         padded storage (``.contiguous()`` gives a dense copy)."""
+        if slab is not None:
+            self._refuse_thin_slabs(slab, reg_z_over_reg)     # first: the one refusal that every rank of a job must raise alike
         if not isinstance(x0, torch.Tensor) or not x0.is_cuda:
             raise ValueError("x0 must be a device tensor (this rank's z-slab of the volume)")
         if x0.dim() != 4:
@@ -261,6 +263,20 @@ class _SlabProblem:
             geo = None
         self.geo = geo if geo is not None else self.geom(0, nz)
         self._geoms[(0, nz)] = self.geo
+
+    HALO_PLANES = 1     # planes of x a kernel reads beyond this rank's slab, per neighbour (``SubgradientDescent``, ``ADMM``: 2)
+
+    def _refuse_thin_slabs(self, s, reg_z_over_reg):
+        """A solver with ``HALO_PLANES`` = 2 cannot serve a rank that holds one plane: that rank would send one plane where its neighbour
+        receives two (``HaloPlan.exchange_image2``), and its plane z0 - 2 belongs to the rank two away.  Decided from ``slab.parts``,
+        which every rank holds identically, and before anything of the constructor communicates (the ghost planes and the maximum
+        of a per-voxel time weight): every rank raises the same error, none is left waiting in a collective.  A volume whose z axis
+        is not regularised (reg_z_over_reg = 0, or one plane in all) exchanges nothing and is served at any partition."""
+        need = self.HALO_PLANES
+        sizes = [n for _, n in s.parts]
+        if need > 1 and s.sharded and s.nz_global > 1 and float(reg_z_over_reg) > 0 and min(sizes) < need:
+            raise ValueError("%s reads %d halo planes from each z-neighbour, so every rank must hold >= %d planes: %d planes over %d ranks "
+                             "are split as %s" % (type(self).__name__, need, need, s.nz_global, s.world, sizes))
 
     def _one_sweep_default(self, sharded_ok):
         """The default-path rule of the Chambolle-Pock solvers: the one-sweep kernel where tv_cp_fused_supported accepts the geometry --
@@ -2230,6 +2246,7 @@ class SubgradientDescent(_SlabProblem):
     interior planes, first two planes, last two planes when the halo exchange is overlapped)."""
 
     SLOTS = 6
+    HALO_PLANES = 2     # the sub-gradient of a site reads x two planes away
 
     @classmethod
     def loss_from_slots(cls, h, regularization):
@@ -2265,9 +2282,7 @@ class SubgradientDescent(_SlabProblem):
             self.x_alt = self.new_image()           # the persistent loop ping-pongs the iterate
         self.ws = self.geo.workspace()
         self.plan = HaloPlan(self.slab, scheme, self.geo.z_active)
-        sh = self.plan.on
-        if sh and min(nz_r for _, nz_r in self.slab.parts) < 2:
-            raise ValueError("the sub-gradient needs two halo planes: every rank must hold >= 2 planes")
+        sh = self.plan.on           # (with two halo planes per neighbour every rank holds >= 2 planes: ``_refuse_thin_slabs``)
         self.xh_prev = self.new_plane(2) if sh and self.slab.prev is not None else None
         self.xh_next = self.new_plane(2) if sh and self.slab.next is not None else None
         self.sh = sh
@@ -2402,6 +2417,8 @@ class ADMM(_SlabProblem):
     the one-sweep path (``keep_z=False`` moves Nd fewer words per voxel), and ``pitch="auto"`` pads ragged rows: ``.x`` is then a strided
     view of padded storage, ``result()`` a dense copy."""
 
+    HALO_PLANES = 2     # the normal operator D^T D of a site reads x two planes away
+
     def __init__(self, x0, regularization, rho, n_cg=10, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0,
                  mask_static=False, factor_reg_static=0, slab=None, single_reduction=True, fused=None, keep_z=True, x_solver=None,
                  pitch="auto", tune_placement=None, persistent=False):
@@ -2474,9 +2491,7 @@ class ADMM(_SlabProblem):
         self.ws = self.geo.workspace()
         self.plan = HaloPlan(self.slab, scheme, self.geo.z_active)
         pl, s_ = self.plan, self.slab
-        sh = pl.on
-        if sh and min(nz_r for _, nz_r in s_.parts) < 2:
-            raise ValueError("the normal operator needs two halo planes: every rank must hold >= 2 planes")
+        sh = pl.on                  # (with two halo planes per neighbour every rank holds >= 2 planes: ``_refuse_thin_slabs``)
         self.sh = sh
         self.h2_prev = self.new_plane(2) if sh and s_.prev is not None else None
         self.h2_next = self.new_plane(2) if sh and s_.next is not None else None

@@ -396,13 +396,14 @@ def clean_phantom(shape):
 def problem(shape, case):
     """(x0, w, lower, upper): the phantom plus N(0, 1) noise, rounded to fp32 so that both precisions see the same data.
     "inpaint": 30 % of the sites unknown (w = 0) and zero-filled, the others w = 1, no box.  "box": w uniform in [0.25, 2.25], the box [0, 18].
-    "shift": those weights with lower = 1 and no upper bound -- a box without 0, which the solver shifts."""
+    "shift": those weights with lower = 1 and no upper bound -- a box without 0, which the solver shifts.
+    "inpaint_box" (tests/test_gpu_thin_slabs.py; not one of ``CASES``): the data of "inpaint" with the box of "box"."""
     rng = np.random.default_rng(0)
     x0 = (clean_phantom(shape) + rng.standard_normal(shape)).astype(np.float32).astype(np.float64)
-    if case == "inpaint":
+    if case in ("inpaint", "inpaint_box"):
         known = rng.random(shape) >= 0.3
         x0[~known] = 0.0
-        out = (x0, known, None, None)
+        out = (x0, known, None, None) if case == "inpaint" else (x0, known, 0.0, 18.0)
     else:
         w = (0.25 + 2.0 * rng.random(shape)).astype(np.float32).astype(np.float64)
         out = (x0, w, 0.0, 18.0) if case == "box" else (x0, w, 1.0, None)

@@ -141,3 +141,79 @@ def test_partition_is_contiguous_and_balanced():
             assert parts[0][0] == 0 and sum(n for _, n in parts) == nz
             assert all(parts[i][0] + parts[i][1] == parts[i + 1][0] for i in range(w - 1))
             assert max(n for _, n in parts) - min(n for _, n in parts) <= 1
+
+
+def test_partition_properties_for_every_small_split():
+    """every 1 <= world <= nz_global <= 12: contiguous from 0, covers [0, nz_global), no empty rank, sizes differ by at most 1"""
+    sys.path.insert(0, PKG)
+    from pytv.slab import Slab, partition
+    for nz in range(1, 13):
+        for w in range(1, nz + 1):
+            parts = partition(nz, w)
+            assert len(parts) == w and parts[0][0] == 0 and parts[-1][0] + parts[-1][1] == nz, (nz, w)
+            assert all(parts[i][0] + parts[i][1] == parts[i + 1][0] for i in range(w - 1)), (nz, w)
+            sizes = [n for _, n in parts]
+            assert min(sizes) >= 1 and max(sizes) - min(sizes) <= 1 and sum(sizes) == nz, (nz, w)
+            for r in range(w):                      # every rank derives the same table and its own row of it
+                s = Slab(nz, rank=r, world=w)
+                assert s.parts == parts and (s.z0, s.nz) == parts[r]
+                assert (s.prev, s.next) == (r - 1 if r > 0 else None, r + 1 if r + 1 < w else None)
+        with pytest.raises(ValueError, match="cannot split"):
+            Slab(nz, rank=0, world=nz + 1)
+
+
+@pytest.mark.parametrize("world,shape", [(3, (4, 2, 4, 5)), (4, (5, 2, 4, 5))])
+def test_halo_exchange_gloo_with_one_plane_ranks(world, shape):
+    """planes 2, 1, 1 and 2, 1, 1, 1: a one-plane rank sends the same plane both ways, and the middle ranks receive from two one-plane
+    neighbours (the two-plane exchange is skipped by ``_worker`` on such a partition: the solvers that need it refuse it)"""
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_worker, args=(world, _free_port(), shape, 1.3, 0.8, ret), nprocs=world, join=True)
+    assert len(ret) == world
+    for rank, errs in ret.items():
+        assert len(errs) == 3 * len(SCHEMES)
+        for k, v in errs.items():
+            assert v < 1e-12, (rank, k, v)
+
+
+def test_two_plane_exchange_refuses_a_one_plane_slab():
+    """no process group here: a refusal that came after the first message would surface as another exception"""
+    sys.path.insert(0, PKG)
+    from pytv.slab import HaloPlan, Slab
+    assert not dist.is_initialized()
+    for nz, w in ((3, 3), (4, 3), (5, 4), (6, 4)):
+        for r in range(w):
+            slab = Slab(nz, rank=r, world=w)
+            x = torch.zeros((slab.nz, 2, 4, 5), dtype=torch.float64)
+            buf = torch.zeros((2, 2, 4, 5), dtype=torch.float64)
+            if slab.nz < 2:
+                with pytest.raises(ValueError, match="two-plane halos need a slab of >= 2 planes"):
+                    HaloPlan(slab, "hybrid", True).exchange_image2(x, buf, buf)
+            assert HaloPlan(slab, "hybrid", False).exchange_image2(x, buf, buf) == []      # z not regularised: nothing travels
+
+
+def test_radius2_solvers_refuse_thin_partitions_before_anything_else():
+    """``SubgradientDescent`` / ``ADMM`` on a partition with a one-plane rank: the same ValueError from every rank index, the ranks
+    that hold two planes included, decided from the partition alone -- before the tensor is looked at (a host tensor here), before
+    the library is asked for anything and before any communication (there is no process group)"""
+    sys.path.insert(0, PKG)
+    from pytv import solvers
+    from pytv.slab import Slab
+    assert not dist.is_initialized()
+    for nz, w in ((3, 3), (4, 3), (5, 4), (6, 4)):
+        for cls, args in ((solvers.SubgradientDescent, (1.0, 1e-3)), (solvers.ADMM, (1.0, 0.1))):
+            texts = set()
+            for r in range(w):
+                slab = Slab(nz, rank=r, world=w)
+                with pytest.raises(ValueError, match="every rank must hold >= 2 planes") as e:
+                    cls(torch.zeros((slab.nz, 2, 4, 5), dtype=torch.float64), *args, slab=slab, mask_static=np.ones((slab.nz, 2, 4, 5)))
+                texts.add(str(e.value))
+            assert len(texts) == 1 and cls.__name__ in min(texts) and str([n for _, n in slab.parts]) in min(texts)
+    # partitions whose ranks all hold two planes pass this check (and fail the next one: the tensor is not on a device)
+    for nz, w in ((8, 3), (7, 2), (9, 2)):
+        slab = Slab(nz, rank=w - 1, world=w)
+        with pytest.raises(ValueError, match="x0 must be a device tensor"):
+            solvers.SubgradientDescent(torch.zeros((slab.nz, 2, 4, 5), dtype=torch.float64), 1.0, 1e-3, slab=slab)
+    # ... and so does a one-plane-halo solver on a one-plane rank
+    with pytest.raises(ValueError, match="x0 must be a device tensor"):
+        solvers.ChambollePock(torch.zeros((1, 2, 4, 5), dtype=torch.float64), 1.0, slab=Slab(4, rank=2, world=3))

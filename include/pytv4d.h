@@ -372,6 +372,44 @@ int tv_cp_dual_wtv(const tv_geom* g, const void* x, const void* x_prev, const vo
 int tv_dual_gap_wtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
                     const void* q_next, const void* x0, const void* gw, double lambda, double* out, void* ws, void* stream);
 
+/* Dual step of Chambolle-Pock for the ADAPTIVE HUBER-TV regulariser: the per-voxel weight g_i >= 0 of tv_cp_dual_wtv on the Huber function of
+ * tv_cp_dual_huber,
+ *   P(x) = 1/2 |x - x0|^2 + lambda sum_i g_i h_alpha(|D x|_{2,i}).
+ * With r_i = lambda g_i the conjugate of a site's term is alpha |q_i|^2 / (2 r_i) + indicator(|q_i|_2 <= r_i); for g_i = 0 it is the indicator of
+ * q_i = 0.  At each site
+ *   shrink_i = r_i / (r_i + sigma_D alpha)               (the constant 0 where r_i = 0; sigma_D alpha > 0, formed once in double: no division by zero)
+ *   v = shrink_i (q + sigma_D D x) per channel,  n = |v|_2;   q <- v where n <= r_i,  v * (r_i / n) beyond,  0 where r_i = 0    (tv_cp_dual_wtv's select)
+ *   *hwtv (device fp64) = sum_i g_i h_alpha(|D x|_{2,i}) of the local planes, h_alpha as (n - a) + a^2 / (2 alpha), a = min(n, alpha), in fp64.
+ * For finite inputs with g >= 0: a site inside its ball keeps q = v bit for bit; a site with g_i = 0 ends with q = +-0 in every channel; the
+ * result is never NaN or Inf; |q|_2 <= r_i up to rounding afterwards.  gw as in tv_cp_dual_wtv: stored like x0, NO halo plane, part of the
+ * 16-byte alignment test, finite and >= 0 by the caller's contract (pytv.solvers.AdaptiveHuberChambollePock checks it once).
+ * 2 Nd + 2 words per voxel; q is written in place, nothing else but hwtv and ws.  x_prev / x_next, alignment and dispatch as tv_cp_dual: four
+ * schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays, mask_static / time_factor / time_weight_vol, z-slabs.  ALWAYS the
+ * one-site-per-thread kernel: there is NO plane-marching form of this epilogue, fp32 planes of >= 4 MiB run the one-site kernel too (on
+ * unsharded volumes tv_cp_hwtv_sweep serves the large planes).  The primal half of the iteration is tv_cp_primal_accel.
+ * TV_E_ARG: a NULL array ("<name> is NULL", gw included), lambda, alpha or sigma_D not finite and > 0 (alpha = 0 is tv_cp_dual_wtv's model and is
+ * refused), a tv_geom of another interface version; a missing halo plane is TV_E_HALO ("x_prev: ..." / "x_next: ..."); all checks precede any
+ * device access. */
+int tv_cp_dual_hwtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q, const void* gw,
+                    double sigma_D, double lambda, double alpha, double* hwtv, void* ws, void* stream);
+
+/* Duality-gap certificate of the adaptive Huber-TV model above for an iterate x and a dual variable q with |q|_2 <= lambda g_i per site (what
+ * tv_cp_dual_hwtv leaves).  Dual(q) = <gd, x0> - 1/2 |gd|^2 - sum_{r_i > 0} alpha |q_i|^2 / (2 r_i) with gd = D^T q, r_i = lambda g_i.  Over the
+ * local planes
+ *   out[0] = sum_i g_i h_alpha(|D x|_{2,i})
+ *   out[1] = 1/2 |x - x0|^2
+ *   out[2] = sum_sites [ 1/2 (x - x0 + gd)^2  +  ( r_i h_alpha(|D x|_2) + [r_i > 0] alpha |q|^2 / (2 r_i) - <q, D x> ) ]  =  P(x) - Dual(q)
+ * Both parts of a site's term are >= 0 (Fenchel-Young).  Where |D x|_2 <= alpha and r_i > 0 the second part is summed as the perfect square
+ * (r_i / 2 alpha) |D x - (alpha / r_i) q|^2.  Accumulated site by site in fp64, never as P - Dual, not clamped.  The caller has
+ * P = out[1] + lambda * out[0], Dual = P - out[2], and 1/2 |x - x*|^2 <= out[2].
+ * REDUCE-ONLY: nothing is written except out (three device fp64 words) and ws.  Halos, gw and geometries as tv_dual_gap_wtv: one launch of the
+ * one-site-per-thread kernel, Nd + 3 words per voxel, large planes too (there is no plane-marching form); slab partials add up to the
+ * unsharded scalars.
+ * TV_E_ARG: a NULL array ("<name> is NULL", gw included), lambda or alpha not finite and > 0, a tv_geom of another interface version; a
+ * missing halo plane is TV_E_HALO ("x_prev: ..." / "x_next: ..." / "q_prev: ..." / "q_next: ..."); all checks precede any device access. */
+int tv_dual_gap_hwtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                     const void* q_next, const void* x0, const void* gw, double lambda, double alpha, double* out, void* ws, void* stream);
+
 /* One-sweep form of the same iteration (all four schemes; fp32, nx % 4 == 0, nx >= 64,
  * any m: more than 8 frames are processed as time windows of 8): q is read and written ONCE per
  * iteration.  x is ping-ponged.
@@ -455,6 +493,20 @@ int tv_cp_accel_fixup(const tv_geom* g, const void* q, const void* q_prev, const
 int tv_cp_huber_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
                       const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double alpha, double tau, double theta,
                       int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* hub, double* fid, void* ws, void* stream);
+/* One-sweep form of the ADAPTIVE HUBER-TV iteration (tv_cp_dual_hwtv on x_bar + tv_cp_primal_accel with constant tau and theta; same
+ * geometries as tv_cp_fused: tv_cp_fused_supported).  tv_cp_huber_sweep with the per-site shrink factor and radius of tv_cp_dual_hwtv:
+ *   tv_cp_hwtv_sweep : q_out <- the dual update of tv_cp_dual_hwtv on (q_in, xbar_in, gw);  x_new, xbar_out, x exactly as tv_cp_accel_sweep,
+ *                      EXCEPT the adjoint terms tv_cp_fused leaves out;  *hwtv = sum_i g_i h_alpha(|D xbar_in|_{2,i}) over the local planes in
+ *                      fp64;  *fid and the flags TV_CP_FID_OF_INPUT / TV_CP_FID_BOTH as tv_cp_accel_sweep
+ * gw of a site is one more streamed 16-byte load per frame: stored like x0, the local planes only, NO halo plane (the projection is local),
+ * part of the 16-byte alignment test.  2 Nd + 6 words per voxel where the pair tv_cp_dual_hwtv + tv_cp_primal_accel moves 3 Nd + 6.
+ * THE FIX-UP OF THIS SWEEP IS tv_cp_accel_fixup, called with the same tau and theta (and q_out).  There is no fix-up symbol of its own.
+ * Flags, chunk ranges, halos, aliasing rules and the bit-for-bit statements about ranges and slabs are those of tv_cp_accel_sweep.  TV_E_ARG,
+ * each with its own message, before any device access: every case tv_cp_accel_sweep refuses, "gw is NULL", and lambda, alpha or sigma_D not
+ * finite and > 0.  A missing halo plane is TV_E_HALO. */
+int tv_cp_hwtv_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
+                     const void* x0, void* x, void* xbar_out, const void* gw, double sigma_D, double lambda, double alpha, double tau,
+                     double theta, int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* hwtv, double* fid, void* ws, void* stream);
 
 /* ---- fused ADMM updates (not in the reference; README.md:26,135 mention only) --------------- */
 /* v = D x + u; z = v * max(0, 1 - thresh/|v|_2); u = v - z; *tv (device fp64) = |D x|_{2,1}. */

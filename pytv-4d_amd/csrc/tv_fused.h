@@ -333,7 +333,10 @@ template <typename T> struct FusedArgsT {
                           // fidelity of the input -- the last sweep of a lagged block returns both, so that no separate reduction closes the block
     // ALG_CPHUB only (at the END: the initialisers of the other entry points stop at part_fid2 and leave these zero, nobody reads them there)
     T shrink;             // 1 / (1 + sigma alpha / lambda), formed in double by the host
-    double alpha, half_inv_alpha;      // the Huber threshold and 1 / (2 alpha) of the partial sum h_alpha(|D x|_2)
+    double alpha, half_inv_alpha;      // the Huber threshold and 1 / (2 alpha) of the partial sum h_alpha(|D x|_2)  (ALG_CPHWT too)
+    // ALG_CPHWT only (after the above, for the same reason)
+    const T* gw;          // the per-voxel weight g of the regulariser, stored like x0: the local planes, NO halo plane (the projection is local)
+    T lambda, sigma_alpha;             // lambda (the radius of a site's ball is lambda g_i) and sigma alpha, formed in double by the host
 };
 using FusedArgs = FusedArgsT<float>;
 
@@ -359,9 +362,24 @@ using FusedArgs = FusedArgsT<float>;
 //            cp_dual_huber_site (tv_stencil.h): v = shrink (q + sigma D x_bar) per channel, then the same projection; the first partial is
 //            sum h_alpha(|D x_bar|_2) per column as (n - a) + a^2 / (2 alpha), a = min(n, alpha), in fp64.  Everything else -- primal epilogue, partial
 //            slots, prefetches -- is ALG_CPACC's (alg_extrapolates), and its fix-up IS ALG_CPACC's: the fix-up only gathers D^T q' terms from the stored q'.
-constexpr int ALG_CP = 0, ALG_ADMM = 1, ALG_CPOP = 2, ALG_CPACC = 3, ALG_CPHUB = 4;
+//   ALG_CPHWT: the ADAPTIVE Huber-TV iteration of AdaptiveHuberChambollePock -- ALG_CPHUB with a per-voxel weight g on the
+//            regulariser and the dual update of cp_dual_hwtv_site (tv_stencil.h): r = lambda g, v = r / (r + sigma alpha) (q + sigma D x_bar) per
+//            channel (0 where r = 0), then the SELECTED projection factor of cp_dual_wtv_site (0, the constant 1, or r / |v|_2).  g of the site is one
+//            more streamed 16-byte load per frame (FusedArgsT::gw, no halo); the first partial is sum g h_alpha(|D x_bar|_2) in fp64.  Everything
+//            else is ALG_CPACC's, the fix-up included.
+constexpr int ALG_CP = 0, ALG_ADMM = 1, ALG_CPOP = 2, ALG_CPACC = 3, ALG_CPHUB = 4, ALG_CPHWT = 5;
 // the ALGs with the state (x, x_bar, q) and the extrapolating primal epilogue
-constexpr bool alg_extrapolates(int alg) { return alg == ALG_CPACC || alg == ALG_CPHUB; }
+constexpr bool alg_extrapolates(int alg) { return alg == ALG_CPACC || alg == ALG_CPHUB || alg == ALG_CPHWT; }
+// the ALGs whose fix-up is the ALG_CPACC one (no k_cp_fixup instantiation of their own): the fix-up only gathers D^T q' terms from the stored q'
+constexpr bool alg_borrows_fixup(int alg) { return alg == ALG_CPHUB || alg == ALG_CPHWT; }
+
+// ALG_CPHWT, hybrid: the single-window instantiations of 7 frames (fp32) and 6 frames (fp64) would carry 24 / 16 bytes of scratch per lane
+// where their ALG_CPHUB siblings have none, and neither PFX nor PFQ is on there to be switched off.  They are NOT instantiated: those
+// volumes run the windowed instantiation as one ragged window of 8, which has no scratch in either dtype (as hybrid volumes of 8 frames do
+// in every ALG, sweep_plan in tv_fused.hip).  The price is LDS for 8 frames where 6 or 7 are used.  fused_sweep_launch applies this ONE rule.
+constexpr bool cphwt_windowed(int alg, int scheme, int m, int elem_bytes) {
+    return alg == ALG_CPHWT && scheme == HYBRID && ((m == 7 && elem_bytes == 4) || (m == 6 && elem_bytes == 8));
+}
 
 // XW: the CP_NW waves of a block exchange their tile-edge column terms through LDS (one barrier per plane)
 // TWIN: time windows for volumes with more than CP_TWN frames -- grid z = window, the block works on the frames
@@ -433,8 +451,13 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
     // -DTV_FUSED_PFQ=2 (profiles/r5f_pfq_ab.txt): ADMM sweep of the configs[4] slab 5.18 -> 4.52 ms (upwind), 5.09 -> 4.51 (downwind);
     // CP sweep of the north-star volume 20.10 -> 19.36 (upwind), 20.85 -> 19.70 (downwind).  Not on narrow frames (XW false: the M >= 5
     // downwind instantiations spill up to 484 B with it) and not in fp64 (unmeasured).  TV_FUSED_PFQ: 0 off, 1 central only, 2 (default) this.
+    // ALG_CPHWT carries the site's weight and shrink factor through the dual update: the fp32 central instantiations of 7 frames and of the
+    // 8-frame window spill with the prefetch (24 / 212 B) where their ALG_CPHUB siblings have no scratch, so they run without it
+    // (profiles/adaptive_huber_regs.txt).  Two hybrid single-window instantiations have neither prefetch to give up and do not exist:
+    // cphwt_windowed() below.
     constexpr bool PFQ = (TV_FUSED_PFQ != 0) && (S == CENTRAL || (TV_FUSED_PFQ == 2 && S != HYBRID && XW && sizeof(T) == 4)) &&
-                         (!TWIN || TV_FUSED_PFQ_TWIN != 0);
+                         (!TWIN || TV_FUSED_PFQ_TWIN != 0) &&
+                         !(ALG == ALG_CPHWT && S == CENTRAL && sizeof(T) == 4 && ((M == 7 && !TWIN) || (M == 8 && TWIN)));
     VT qpre[PFQ ? 4 : 1];
     if (PFQ) {
 #pragma unroll
@@ -638,6 +661,10 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
             // (every q' sample is scaled by its own voxel's factor before the difference): round 3
             VT mft = mf;
             if (g.wv != nullptr && g.ta && c.ok) mft = mf * ldu_s_t<T, V>(static_cast<const T*>(g.wv) + (long long)z * g.s_z + toff, voff);
+            VT gwv = zero;            // ALG_CPHWT: the weight g of this site, one more streamed read per frame
+            if constexpr (ALG == ALG_CPHWT) {
+                if (c.ok) gwv = ldu_s_t<T, V>(a.gw + (long long)z * g.s_z + toff, voff);
+            }
             // ------------------------------------------------ neighbourhood of x(z, t)
             XN<T, V> n;
             n.c = C[t];
@@ -702,10 +729,13 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
             const T* qbase_in = a.q_in + (long long)z * g.s_dz + toff;        // uniform (== qbase unless q is ping-ponged)
             VT vs = zero;
             if (c.ok) {
+                VT shr = zero;        // ALG_CPHWT: the site's own shrink factor r / (r + sigma alpha), 0 where r = 0 (cp_dual_hwtv_site)
+                if constexpr (ALG == ALG_CPHWT) shr = hwtv_shrink<T, V>(gwv, a.lambda, a.sigma_alpha);
                 for_each_channel<S>(g, [&](auto slot, int ch) {
                     constexpr int k = decltype(slot)::value;
                     const VT qv = PFQ ? qcur[k & 3] : ldu_s_t<T, V>(qbase_in + (long long)ch * g.s_z, voff);
                     if constexpr (ALG == ALG_CPHUB) v[k] = a.shrink * (qv + a.sigma * o[k]);      // shrink, then project (cp_dual_huber_site)
+                    else if constexpr (ALG == ALG_CPHWT) v[k] = shr * (qv + a.sigma * o[k]);
                     else v[k] = (ALG == ALG_ADMM) ? o[k] + qv : qv + a.sigma * o[k];
                     vs = vs + v[k] * v[k];
                 });
@@ -745,14 +775,17 @@ __global__ __launch_bounds__(64 * CP_NW, TV_WAVES ? TV_WAVES : 2) void k_cp_fuse
                 } else {
 #pragma unroll
                     for (int i = 0; i < V; ++i) {
-                        if constexpr (ALG == ALG_CPHUB) {         // h_alpha(|D x_bar|_2): no branch, fp64
+                        if constexpr (ALG == ALG_CPHUB || ALG == ALG_CPHWT) {         // h_alpha(|D x_bar|_2): no branch, fp64
                             const double n = (double)tsqrt(ds.v[i]);
                             const double ha = fmin(n, a.alpha);
-                            acc_tv += (n - ha) + ha * ha * a.half_inv_alpha;
+                            const double h = (n - ha) + ha * ha * a.half_inv_alpha;
+                            if constexpr (ALG == ALG_CPHWT) acc_tv += (double)gwv.v[i] * h;
+                            else acc_tv += h;
                         } else {
                             acc_tv += (double)tsqrt(ds.v[i]);
                         }
-                        scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * a.inv_lambda);
+                        if constexpr (ALG == ALG_CPHWT) scale.v[i] = wtv_scale<T>(tsqrt(vs.v[i]), a.lambda * gwv.v[i]);
+                        else scale.v[i] = T(1) / tmax(T(1), tsqrt(vs.v[i]) * a.inv_lambda);
                     }
                     for_each_channel<S>(g, [&](auto slot, int ch) {
                         constexpr int k = decltype(slot)::value;

@@ -249,35 +249,41 @@ static int cp_accel_steps_ok(double tau, double theta) {
     return 0;
 }
 
-// the body of tv_cp_accel_sweep and tv_cp_huber_sweep: ALG_CPACC, or ALG_CPHUB with the Huber threshold alpha
+// the body of tv_cp_accel_sweep, tv_cp_huber_sweep and tv_cp_hwtv_sweep: ALG_CPACC, ALG_CPHUB with the Huber threshold alpha, or ALG_CPHWT with
+// alpha and the per-voxel weight gw (NULL for the other two)
 extern "C++" {
 template <int ALG>
 static int cp_accel_sweep_impl(const char* who, const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in,
-                               void* q_out, const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double alpha, double tau,
-                               double theta, int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* tvout, double* fid, void* ws,
-                               void* stream) {
+                               void* q_out, const void* x0, void* x, void* xbar_out, const void* gw, double sigma_D, double lambda, double alpha,
+                               double tau, double theta, int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* tvout, double* fid,
+                               void* ws, void* stream) {
     DG d;
     if (int rc = make_dg(g, d, true)) return rc;
     if (!xbar_in || !q_in || !q_out || !x0 || !x || !xbar_out || !tvout || !fid || !ws) return fail(TV_E_ARG, "NULL array");
+    if (ALG == ALG_CPHWT && !gw) return fail(TV_E_ARG, "gw is NULL");
     if (xbar_in == xbar_out) return fail(TV_E_ARG, "xbar_in and xbar_out must be different buffers (ping-pong)");
     if (x == xbar_in || x == xbar_out || x == x0) return fail(TV_E_ARG, "x must not alias xbar_in, xbar_out or x0");
     if (!(lambda > 0.0)) return fail(TV_E_ARG, "lambda must be > 0");
     if (ALG == ALG_CPHUB && !finite_pos(alpha)) return fail(TV_E_ARG, "alpha must be a finite number > 0 (alpha = 0 is plain TV: tv_cp_accel_sweep)");
+    if (ALG == ALG_CPHWT && !finite_pos(lambda)) return fail(TV_E_ARG, "lambda must be a finite number > 0");
+    if (ALG == ALG_CPHWT && !finite_pos(alpha)) return fail(TV_E_ARG, "alpha must be a finite number > 0");
+    if (ALG == ALG_CPHWT && !finite_pos(sigma_D)) return fail(TV_E_ARG, "sigma_D must be a finite number > 0");
     if (int rc = cp_accel_steps_ok(tau, theta)) return rc;
     if (flags & ~(TV_CP_FID_OF_INPUT | TV_CP_FID_BOTH)) return fail(TV_E_ARG, (std::string(who) + ": unknown flag").c_str());
     if ((flags & TV_CP_FID_BOTH) && !(flags & TV_CP_FID_OF_INPUT))
         return fail(TV_E_ARG, (std::string(who) + ": TV_CP_FID_BOTH extends TV_CP_FID_OF_INPUT").c_str());
     if (!tv_cp_fused_supported(g)) return fail(TV_E_ARG, "geometry not supported by the one-sweep path");
-    if (!aligned16({xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
+    if (!aligned16({xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, gw, d.wv})) return fail(TV_E_ARG, "arrays must be 16-byte aligned");
     const double inv_1p_tau = 1.0 / (1.0 + tau);
     // ALG_CPHUB: shrink = 1 / (1 + sigma alpha / lambda) and 1 / (2 alpha) formed in double, as tv_cp_dual_huber forms them
+    // ALG_CPHWT: sigma alpha and 1 / (2 alpha), as tv_cp_dual_hwtv forms them (the shrink factor is per site)
     const double shrink = (ALG == ALG_CPHUB) ? 1.0 / (1.0 + sigma_D * alpha / lambda) : 1.0;
-    const double half_inv_alpha = (ALG == ALG_CPHUB) ? 0.5 / alpha : 0.0;
+    const double half_inv_alpha = (ALG == ALG_CPHUB || ALG == ALG_CPHWT) ? 0.5 / alpha : 0.0;
     auto args = [&]<typename T>(const Partials& P) {          // theta and 1 / (1 + tau) in the fields of sigma_A; slot 2: TV_CP_FID_BOTH only
         return FusedArgsT<T>{(const T*)xbar_in, (const T*)xbar_prev, (const T*)xbar_next, (T*)q_out, (const T*)x0, (T*)x,
                              (T*)xbar_out, (T)sigma_D, (T)(1.0 / lambda), (T)tau, (T)theta, (T)inv_1p_tau, P.slot(0), P.slot(1),
                              ((flags & TV_CP_FID_OF_INPUT) ? 2 : 0) | ((flags & TV_CP_FID_BOTH) ? 4 : 0), (const T*)q_in, P.slot(2),
-                             (T)shrink, alpha, half_inv_alpha};
+                             (T)shrink, alpha, half_inv_alpha, (const T*)gw, (T)lambda, (T)(sigma_D * alpha)};
     };
     return run_sweep<ALG>(g, d, xbar_in, xbar_prev, xbar_next, chunk_begin, chunk_count, ws, (hipStream_t)stream, tvout, fid,
                           (flags & TV_CP_FID_BOTH) ? 2 : 1, args);
@@ -287,7 +293,7 @@ static int cp_accel_sweep_impl(const char* who, const tv_geom* g, const void* xb
 int tv_cp_accel_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
                       const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double tau, double theta, int32_t flags,
                       int64_t chunk_begin, int64_t chunk_count, double* tvout, double* fid, void* ws, void* stream) {
-    return cp_accel_sweep_impl<ALG_CPACC>("tv_cp_accel_sweep", g, xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, sigma_D, lambda, 0.0, tau,
+    return cp_accel_sweep_impl<ALG_CPACC>("tv_cp_accel_sweep", g, xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, nullptr, sigma_D, lambda, 0.0, tau,
                                           theta, flags, chunk_begin, chunk_count, tvout, fid, ws, stream);
 }
 
@@ -296,8 +302,17 @@ int tv_cp_accel_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_pr
 int tv_cp_huber_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
                       const void* x0, void* x, void* xbar_out, double sigma_D, double lambda, double alpha, double tau, double theta,
                       int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* hub, double* fid, void* ws, void* stream) {
-    return cp_accel_sweep_impl<ALG_CPHUB>("tv_cp_huber_sweep", g, xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, sigma_D, lambda, alpha, tau,
+    return cp_accel_sweep_impl<ALG_CPHUB>("tv_cp_huber_sweep", g, xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, nullptr, sigma_D, lambda, alpha, tau,
                                           theta, flags, chunk_begin, chunk_count, hub, fid, ws, stream);
+}
+
+// One-sweep ADAPTIVE HUBER-TV Chambolle-Pock (tv_fused.h, ALG_CPHWT; include/pytv4d.h): tv_cp_accel_sweep with the dual update of tv_cp_dual_hwtv and
+// one more streamed array, the weight gw; *hwtv = sum g h_alpha(|D xbar_in|_2).  Its fix-up is tv_cp_accel_fixup with the same tau and theta.
+int tv_cp_hwtv_sweep(const tv_geom* g, const void* xbar_in, const void* xbar_prev, const void* xbar_next, const void* q_in, void* q_out,
+                     const void* x0, void* x, void* xbar_out, const void* gw, double sigma_D, double lambda, double alpha, double tau, double theta,
+                     int32_t flags, int64_t chunk_begin, int64_t chunk_count, double* hwtv, double* fid, void* ws, void* stream) {
+    return cp_accel_sweep_impl<ALG_CPHWT>("tv_cp_hwtv_sweep", g, xbar_in, xbar_prev, xbar_next, q_in, q_out, x0, x, xbar_out, gw, sigma_D, lambda, alpha,
+                                          tau, theta, flags, chunk_begin, chunk_count, hwtv, fid, ws, stream);
 }
 
 // its fix-up: the missing adjoint terms m go to both arrays, x -= c (s m) and x_bar -= (1 + theta) c (s m) with c = tau / (1 + tau)

@@ -1,6 +1,7 @@
 // tv_fused_launch.h -- launch templates of the one-sweep kernels (tv_fused.h).  One (dtype, ALG) pair per translation unit
 // (tv_fused.hip: float CP, tv_fused_f64.hip: double CP, tv_fused_admm.hip / tv_fused_admm_f64.hip: ADMM, tv_fused_cpop*.hip: the
-// operator sweep, tv_fused_cpacc*.hip: the accelerated iteration, tv_fused_cphub*.hip: the Huber-TV iteration) so that the
+// operator sweep, tv_fused_cpacc*.hip: the accelerated iteration, tv_fused_cphub*.hip: the Huber-TV iteration, tv_fused_cphwt*.hip: the adaptive
+// Huber-TV iteration) so that the
 // sets of instantiations compile next to each other; the extern "C" entry points and the launch geometry live in tv_fused.hip.
 #pragma once
 #include "tv_host.h"
@@ -23,8 +24,11 @@ template <typename T, int ALG>
 static int fused_sweep_launch(const tv_geom* g, const DG& d, const LC& lc, hipStream_t st, const FusedArgsT<T>& a, int zc, int chunk0, bool xw,
                               bool force_win) {
     if (ALG != ALG_CP && !xw) return fail(TV_E_ARG, "the ADMM / operator / accelerated sweeps are built with TV_FUSED_XW=1 only");
-    return dispatch_scheme_m(WindowedMs{}, g->scheme, (d.m > CP_TWN || force_win) ? 0 : d.m, kNoFusedSM, [&]<int S, int M>() -> int {
-        if constexpr (M == 0) {          // M > 8: windows of 8 frames
+    const bool win = d.m > CP_TWN || force_win || cphwt_windowed(ALG, g->scheme, d.m, (int)sizeof(T));
+    return dispatch_scheme_m(WindowedMs{}, g->scheme, win ? 0 : d.m, kNoFusedSM, [&]<int S, int M>() -> int {
+        if constexpr (cphwt_windowed(ALG, S, M, (int)sizeof(T))) {
+            return fail(TV_E_ARG, kNoFusedSM);          // (not reached: `win` sends these to M == 0)
+        } else if constexpr (M == 0) {          // M > 8: windows of 8 frames, or one ragged window (force_win, cphwt_windowed)
             if (xw) hipLaunchKernelGGL((k_cp_fused<S, CP_TWN, true, true, T, ALG>), lc.grid, lc.block, 0, st, d, make_w<T>(g), a, zc, chunk0);
             else if constexpr (ALG == ALG_CP)
                 hipLaunchKernelGGL((k_cp_fused<S, CP_TWN, false, true, T, ALG>), lc.grid, lc.block, 0, st, d, make_w<T>(g), a, zc, chunk0);
@@ -39,12 +43,12 @@ static int fused_sweep_launch(const tv_geom* g, const DG& d, const LC& lc, hipSt
 template <typename T, int ALG>
 static int fused_fixup_launch(const tv_geom* g, const DG& d, hipStream_t st, const FixupArgsT<T>& a, const FixPlan& p, double* w0) {
     if (ALG != ALG_CP && !p.xw) return fail(TV_E_ARG, "the ADMM / operator / accelerated sweeps are built with TV_FUSED_XW=1 only");
-    // the Huber-TV sweep has no fix-up kernel of its own (no k_cp_fixup instantiation): tv_cp_accel_fixup, ALG_CPACC, serves it unchanged
-    if (ALG == ALG_CPHUB) return fail(TV_E_ARG, "internal: the fix-up of the Huber-TV sweep is the ALG_CPACC one");
+    // the Huber-TV sweeps have no fix-up kernel of their own (no k_cp_fixup instantiation): tv_cp_accel_fixup, ALG_CPACC, serves them unchanged
+    if (alg_borrows_fixup(ALG)) return fail(TV_E_ARG, "internal: the fix-up of the Huber-TV sweeps is the ALG_CPACC one");
     const dim3 blk(64, 4, 1);
     return dispatch_scheme(g->scheme, [&]<int S>() -> int {
         auto launch = [&]<bool XW>() -> int {
-            if constexpr ((ALG == ALG_CP || XW) && ALG != ALG_CPHUB) {
+            if constexpr ((ALG == ALG_CP || XW) && !alg_borrows_fixup(ALG)) {
                 hipLaunchKernelGGL((k_cp_fixup<S, 0, XW, T, ALG>), p.g0, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0);
                 if (d.za) hipLaunchKernelGGL((k_cp_fixup<S, 1, XW, T, ALG>), p.g1, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0);
                 hipLaunchKernelGGL((k_cp_fixup<S, 2, XW, T, ALG>), p.g2, blk, 0, st, d, make_w<T>(g), a, p.zc, p.zb, p.zn, w0 + p.n0 + p.n1);

@@ -358,7 +358,7 @@ template <typename T> struct StoreDArgs; template <typename T> struct CpDualArgs
 template <typename T> struct AdmmZUArgs; template <typename T> struct GapDArgs; template <typename T> struct StoreDTArgs;
 template <typename T> struct AxpyDTArgs; template <typename T> struct CpPrimalArgs; template <typename T> struct CpPrimalAccelArgs;
 template <typename T> struct CpPrimalProxArgs; template <typename T> struct CpPrimalKLArgs; template <typename T> struct GapDTArgs;
-template <typename T> struct CpPrimalWLSArgs; template <typename T> struct CpDualWtvArgs;
+template <typename T> struct CpPrimalWLSArgs; template <typename T> struct CpDualWtvArgs; template <typename T> struct CpDualHwtvArgs;
 }
 namespace tvm {
 // D x with the epilogue whose arguments are given (fp32): one overload per epilogue, each a line in tv_march_D.hip
@@ -366,6 +366,7 @@ int D_march(Call& c, const StoreDArgs<float>& a);
 int D_march(Call& c, const CpDualArgs<float>& a);
 int D_march(Call& c, const CpDualHuberArgs<float>& a);       // not where wide16(scheme, M)
 int D_march(Call& c, const CpDualWtvArgs<float>& a);         // not where wtv_spill16(scheme, M)
+int D_march(Call& c, const CpDualHwtvArgs<float>& a);        // NO marching form (tv_march_D.hip): the overload run_D names, it refuses
 int D_march(Call& c, const AdmmZUArgs<float>& a);
 // duality gap, reduce-only (tv_dual_gap): the D^T-side pass (DT_march with GapDTArgs) writes per-block sums of 1/2 (x - x0 + qscale D^T q)^2,
 // the D-side pass (same grid, launched after it) writes |D x|_{2,1} and 1/2 |x - x0|^2 and ADDS sum (lambda |D x|_2 - qscale <q, D x>) to

@@ -8,6 +8,7 @@
 //                CpDual   -> q <- proj(q + sigma D x)            (tv_cp_dual)
 //                CpDualHuber -> the same with the Huber-TV shrink (tv_cp_dual_huber)
 //                CpDualWtv   -> the same with a per-voxel radius lambda g_i (tv_cp_dual_wtv)
+//                CpDualHwtv  -> the two combined: per-voxel shrink and radius (tv_cp_dual_hwtv)
 //                AdmmZU   -> z/u update of ADMM                  (tv_admm_zu)
 //   k_DT     : transposed operator as a GATHER (no atomics, no scratch time buffer) with
 //                StoreDT / AxpyDT / CpPrimal / CpPrimalAccel epilogues   (tv_DT, tv_DT_axpy, tv_cp_primal, tv_cp_primal_accel)
@@ -17,6 +18,7 @@
 //   k_gap    : both of the above at one site, reduce-only: the duality gap of (x, q)  (tv_dual_gap)
 //   k_gap_huber : the same for the Huber-TV regulariser  (tv_dual_gap_huber)
 //   k_gap_wtv   : the same for the spatially adaptive regulariser lambda sum g_i |D x|_2  (tv_dual_gap_wtv)
+//   k_gap_hwtv  : the same for the adaptive Huber-TV regulariser lambda sum g_i h_alpha(|D x|_2)  (tv_dual_gap_hwtv)
 //   k_cp_res : CpDual's site arithmetic, reduce-only: what the next dual update would change  (tv_cp_dual_residual)
 //   k_subgrad_vec / k_subgrad_central_vec : sub-gradient from x and 1/|Dx| (tv_subgrad pass 2)
 //   k_normal_vec  / k_normal_central_vec  : x + rho D^T D x from x alone   (tv_normal_op)
@@ -176,6 +178,47 @@ __global__ __launch_bounds__(256) void k_gap_wtv(DG g, WT<T> w, const T* x, cons
     const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
     const double wtv = block_sum(a[0], sm);
     if (first) p_wtv[b] = wtv;
+    const double fid = block_sum(a[1], sm);
+    if (first) p_fid[b] = fid;
+    const double gap = block_sum(a[2], sm);
+    if (first) p_gap[b] = gap;
+}
+
+// the adaptive Huber-TV form of k_gap (tv_dual_gap_hwtv): k_gap_wtv with the two Huber terms -- the three sums of gap_terms_hwtv (tv_stencil.h)
+template <int S, typename T, int V> struct GapSiteHwtv {
+    static constexpr bool REDUCES = true;
+    WT<T> w;
+    SrcScaled<T, V> src;     // (scale 1, as in GapSiteHuber)
+    const T* x;
+    const T* x0;
+    const T* gw;
+    double lambda, alpha, half_inv_alpha;
+    double* acc3;        // the calling thread's three sums
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        long long inpl;
+        const Vec<T, V> gd = dt_site<S, T, V>(g, w, src, c, inpl);
+        const long long offd = (long long)c.zl * g.s_dz + inpl, off = (long long)c.zl * g.s_z + inpl;
+        Vec<T, V> qv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) qv[k] = vsplat<T, V>(T(0));
+        for_each_channel<S>(g, [&](auto slot, int ch) { qv[decltype(slot)::value] = src.ld(offd + (long long)ch * g.s_z); });
+        gap_terms_hwtv<T, V>(o, qv, vload<T, V>(x + off), vload<T, V>(x0 + off), vload<T, V>(gw + off), gd, lambda, alpha, half_inv_alpha,
+                             acc3[0], acc3[1], acc3[2]);
+        return 0.0;
+    }
+};
+template <int S, typename T, int V>
+__global__ __launch_bounds__(256) void k_gap_hwtv(DG g, WT<T> w, const T* x, const T* xp, const T* xn, SrcScaled<T, V> src, const T* x0,
+                                                   const T* gw, double lambda, double alpha, double half_inv_alpha, double* p_hwtv,
+                                                   double* p_fid, double* p_gap) {
+    __shared__ double sm[16];
+    const Coord c = thread_coord<V>(g, 0);
+    double a[3] = {0.0, 0.0, 0.0};
+    d_site<S, T, V>(g, w, x, xp, xn, 1, c, GapSiteHwtv<S, T, V>{w, src, x, x0, gw, lambda, alpha, half_inv_alpha, a}, PlainMem());
+    const long long b = linear_block_id();
+    const bool first = (threadIdx.x == 0 && threadIdx.y == 0);
+    const double hwtv = block_sum(a[0], sm);
+    if (first) p_hwtv[b] = hwtv;
     const double fid = block_sum(a[1], sm);
     if (first) p_fid[b] = fid;
     const double gap = block_sum(a[2], sm);
@@ -1106,6 +1149,27 @@ int tv_cp_dual_wtv(const tv_geom* g, const void* x, const void* x_prev, const vo
     }, P, wtv);
 }
 
+// Dual step for the adaptive Huber-TV regulariser lambda sum g_i h_alpha(|D x|_2) (include/pytv4d.h): tv_cp_dual_wtv's checks and tv_cp_dual_huber's
+// alpha, with the CpDualHwtv epilogue.  sigma alpha and 1 / (2 alpha) are formed here in double.  ALWAYS the one-site kernel: the epilogue has no
+// marching instantiation (tv_march_D.hip), so fp32 planes of >= 4 MiB run it too.  Every argument check precedes the first device access.
+int tv_cp_dual_hwtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q, const void* gw, double sigma_D,
+                    double lambda, double alpha, double* hwtv, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (int rc = wtv_null({{"x", x}, {"q", q}, {"gw", gw}, {"hwtv", hwtv}, {"ws", ws}})) return rc;
+    if (!finite_pos(lambda)) return fail(TV_E_ARG, "lambda must be a finite number > 0");
+    if (!finite_pos(alpha)) return fail(TV_E_ARG, "alpha must be a finite number > 0 (alpha = 0 is plain adaptive TV: tv_cp_dual_wtv)");
+    if (!finite_pos(sigma_D)) return fail(TV_E_ARG, "sigma_D must be a finite number > 0");
+    if (int rc = wtv_halo(check_x_halos(g, d, x_prev, x_next), "x_prev", "x_next")) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, gw, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);
+    Call c{g, d, x, x_prev, x_next, st};
+    return run_D<CpDualHwtv>(c, vec, false, [&]<typename T>() {
+        return CpDualHwtvArgs<T>{(T*)q, (const T*)gw, (T)sigma_D, (T)lambda, (T)(sigma_D * alpha), alpha, 0.5 / alpha, P.slot(0)};
+    }, P, hwtv);
+}
+
 int tv_cp_primal(const tv_geom* g, const void* q, const void* q_prev, const void* q_next, void* x, const void* x0,
                  void* p, double tau, double sigma_A, double* fid, void* ws, void* stream) {
     DG d;
@@ -1313,6 +1377,30 @@ int tv_dual_gap_wtv(const tv_geom* g, const void* x, const void* x_prev, const v
         SrcScaled<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next, T(1)};
         hipLaunchKernelGGL((k_gap_wtv<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
                            src, (const T*)x0, (const T*)gw, lambda, P.slot(0), P.slot(1), P.slot(2));
+        HIP_TRY(hipGetLastError());
+        return P.reduce_n(3, lc.nblocks, out, st);
+    });
+}
+
+// P(x) - Dual(q) of the adaptive Huber-TV model, with its two by-products; reduce-only (include/pytv4d.h).  Always the one-site kernel,
+// large planes too, as tv_dual_gap_wtv.  Every argument check precedes the first device access.
+int tv_dual_gap_hwtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                     const void* q_next, const void* x0, const void* gw, double lambda, double alpha, double* out, void* ws, void* stream) {
+    DG d;
+    if (int rc = make_dg(g, d, true)) return rc;
+    if (int rc = wtv_null({{"x", x}, {"q", q}, {"x0", x0}, {"gw", gw}, {"out", out}, {"ws", ws}})) return rc;
+    if (!finite_pos(lambda)) return fail(TV_E_ARG, "lambda must be a finite number > 0");
+    if (!finite_pos(alpha)) return fail(TV_E_ARG, "alpha must be a finite number > 0 (alpha = 0 is plain adaptive TV: tv_dual_gap_wtv)");
+    if (int rc = wtv_halo(check_x_halos(g, d, x_prev, x_next), "x_prev", "x_next")) return rc;
+    if (int rc = wtv_halo(check_y_halos(g, d, q_prev, q_next), "q_prev", "q_next")) return rc;
+    const bool vec = rows_vectorisable(g, d) && aligned16({x, x_prev, x_next, q, q_prev, q_next, x0, gw, d.wv});
+    hipStream_t st = (hipStream_t)stream;
+    const Partials P(ws, d);                              // slot 0: sum g_i h_alpha(|D x|_2), slot 1: 1/2 |x - x0|^2, slot 2: the gap
+    return dispatch(g->scheme, g->dtype, vec, [&]<int S, typename T, int V>() -> int {
+        LC lc = launch_cfg(d, V, d.nz);
+        SrcScaled<T, V> src{(const T*)q, (const T*)q_prev, (const T*)q_next, T(1)};
+        hipLaunchKernelGGL((k_gap_hwtv<S, T, V>), lc.grid, lc.block, 0, st, d, make_w<T>(g), (const T*)x, (const T*)x_prev, (const T*)x_next,
+                           src, (const T*)x0, (const T*)gw, lambda, alpha, 0.5 / alpha, P.slot(0), P.slot(1), P.slot(2));
         HIP_TRY(hipGetLastError());
         return P.reduce_n(3, lc.nblocks, out, st);
     });

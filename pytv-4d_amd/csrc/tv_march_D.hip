@@ -28,6 +28,9 @@ int D_march(Call& c, const StoreDArgs<float>& a) { return launch_D_march<StoreD>
 int D_march(Call& c, const CpDualArgs<float>& a) { return launch_D_march<CpDual>(c, a); }
 int D_march(Call& c, const CpDualHuberArgs<float>& a) { return launch_D_march<CpDualHuber, wide16>(c, a); }
 int D_march(Call& c, const CpDualWtvArgs<float>& a) { return launch_D_march<CpDualWtv, wtv_spill16>(c, a); }
+// CpDualHwtv is NOT instantiated in k_D_march: CpDualWtv already leaves (central, 8) one wave per SIMD and spills with 16 frames, and this
+// epilogue carries more per site.  tv_cp_dual_hwtv never asks for the marching form; the one-site kernel runs on every geometry.
+int D_march(Call&, const CpDualHwtvArgs<float>&) { return fail(TV_E_ARG, kNoMarchSM); }
 int D_march(Call& c, const AdmmZUArgs<float>& a) { return launch_D_march<AdmmZU>(c, a); }
 int D_march(Call& c, const GapDArgs<float>& a) { return launch_D_march<GapD>(c, a); }
 int D_norms(const tv_geom* g, const DG& d, const void* x, const void* xp, const void* xn, hipStream_t st, long long* nb,

@@ -322,6 +322,8 @@ template <int S, typename T, int V> struct CpDualHuber : CpDualHuberArgs<T> {
 //   n <= r           ->  the constant 1: v * 1 is v bit for bit (IEEE), never v times a COMPUTED factor that may round off 1
 //   n > r            ->  r / n, evaluated for the result only here, where n > r > 0: no 0 / 0 or x / 0 reaches q
 // Returns sum over the columns of g_i |D x|_2 in fp64.  gw is the weight at the site (read once: non-temporal).  cp_dual_site's sibling.
+// wtv_scale: that selected factor for one column, n = |v|_2 and r = lambda g_i (also the one-sweep kernel's, tv_fused.h ALG_CPHWT).
+template <typename T> __device__ __forceinline__ T wtv_scale(T n, T r) { return (r > T(0)) ? ((n > r) ? r / n : T(1)) : T(0); }
 template <int S, typename T, int V>
 __device__ __forceinline__ double cp_dual_wtv_site(const DG& g, const T* base, const Vec<T, V> (&o)[8], const Vec<T, V>& gw, T sigma, T lambda,
                                                    Vec<T, V> (&v)[8], Vec<T, V>& scale) {
@@ -337,7 +339,7 @@ __device__ __forceinline__ double cp_dual_wtv_site(const DG& g, const T* base, c
     for (int i = 0; i < V; ++i) {
         const T n = tsqrt(vs.v[i]), r = lambda * gw.v[i];
         acc += (double)gw.v[i] * (double)tsqrt(ds.v[i]);
-        scale.v[i] = (r > T(0)) ? ((n > r) ? r / n : T(1)) : T(0);
+        scale.v[i] = wtv_scale<T>(n, r);
     }
     return acc;
 }
@@ -351,6 +353,62 @@ template <int S, typename T, int V> struct CpDualWtv : CpDualWtvArgs<T> {
         Vec<T, V> v[8];
         Vec<T, V> scale;
         const double acc = cp_dual_wtv_site<S, T, V>(g, base, o, gv, this->sigma, this->lambda, v, scale);
+        for_each_channel<S>(g, [&](auto slot, int ch) {
+            constexpr int k = decltype(slot)::value;
+            vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);
+        });
+        return acc;
+    }
+};
+
+// Chambolle-Pock dual update for the ADAPTIVE HUBER-TV regulariser lambda sum g_i h_alpha(|D x|_{2,i}), g_i >= 0 per voxel (tv_cp_dual_hwtv):
+// the two above combined.  With r = lambda g_i the conjugate of a site's term is alpha |q|^2 / (2 r) + indicator(|q|_2 <= r) (g_i = 0: the
+// indicator of q = 0), so its prox shrinks by the site's OWN factor and projects onto the site's own ball.  The arithmetic of one site:
+//   shrink = r / (r + sigma alpha) per column, the constant 0 where r = 0 (sigma alpha > 0 is formed in double by the host: no x / 0)
+//   v      = shrink (q + sigma D x) per channel,  n = |v|_2
+//   q     <- v * wtv_scale(n, r): the select of cp_dual_wtv_site -- inside its ball a site keeps v bit for bit, g_i = 0 keeps q = +-0
+// Returns sum over the columns of g_i h_alpha(|D x|_2) in fp64, h_alpha in the branch-free form of cp_dual_huber_site.
+template <typename T, int V> __device__ __forceinline__ Vec<T, V> hwtv_shrink(const Vec<T, V>& gw, T lambda, T sigma_alpha) {
+    Vec<T, V> sh;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const T r = lambda * gw.v[i];
+        sh.v[i] = (r > T(0)) ? r / (r + sigma_alpha) : T(0);
+    }
+    return sh;
+}
+template <int S, typename T, int V>
+__device__ __forceinline__ double cp_dual_hwtv_site(const DG& g, const T* base, const Vec<T, V> (&o)[8], const Vec<T, V>& gw, T sigma, T lambda,
+                                                    T sigma_alpha, double alpha, double half_inv_alpha, Vec<T, V> (&v)[8], Vec<T, V>& scale) {
+    const Vec<T, V> shrink = hwtv_shrink<T, V>(gw, lambda, sigma_alpha);
+    Vec<T, V> vs = vsplat<T, V>(T(0));
+    for_each_channel<S>(g, [&](auto slot, int ch) {
+        constexpr int k = decltype(slot)::value;
+        v[k] = shrink * (vload_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z) + sigma * o[k]);
+        vs = vs + v[k] * v[k];
+    });
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const double n = (double)tsqrt(ds.v[i]);
+        const double a = fmin(n, alpha);
+        acc += (double)gw.v[i] * ((n - a) + (a * a) * half_inv_alpha);
+        scale.v[i] = wtv_scale<T>(tsqrt(vs.v[i]), lambda * gw.v[i]);
+    }
+    return acc;
+}
+template <typename T> struct CpDualHwtvArgs { T* q; const T* gw; T sigma, lambda, sigma_alpha; double alpha, half_inv_alpha; double* partials; };
+template <int S, typename T, int V> struct CpDualHwtv : CpDualHwtvArgs<T> {
+    static constexpr bool REDUCES = true;
+    __device__ __forceinline__ double operator()(const DG& g, const Coord& c, const Vec<T, V> (&o)[8]) const {
+        const long long inpl = (long long)c.t * g.s_t + (long long)c.y * g.rp + c.col0;
+        T* base = this->q + (long long)c.zl * g.s_dz + inpl;
+        const Vec<T, V> gv = vload_s<T, V>(this->gw + (long long)c.zl * g.s_z + inpl);
+        Vec<T, V> v[8];
+        Vec<T, V> scale;
+        const double acc = cp_dual_hwtv_site<S, T, V>(g, base, o, gv, this->sigma, this->lambda, this->sigma_alpha, this->alpha,
+                                                      this->half_inv_alpha, v, scale);
         for_each_channel<S>(g, [&](auto slot, int ch) {
             constexpr int k = decltype(slot)::value;
             vstore_s<T, V, S == CENTRAL>(base + (long long)ch * g.s_z, v[k] * scale);
@@ -812,6 +870,40 @@ __device__ __forceinline__ void gap_terms_wtv(const Vec<T, V> (&o)[8], const Vec
         a_fid += 0.5 * e * e;
         a_gap += 0.5 * r * r + (lambda * gn - (double)dot.v[i]);
     }
+}
+// The same three terms for the adaptive Huber-TV model 1/2 |x - x0|^2 + lambda sum g_i h_alpha(|D x|_{2,i}) at (x, q), |q|_2 <= r_i = lambda g_i per
+// site and q = 0 where g_i = 0 (tv_dual_gap_hwtv).  a_hwtv receives g_i h_alpha(|D x|_2); the site's gap term is
+//   1/2 (x - x0 + gd)^2  +  ( r_i h_alpha(n) + [r_i > 0] alpha |q|^2 / (2 r_i) - <q, D x> ),    n = |D x|_2,
+// both parts >= 0 (Fenchel-Young).  As in gap_terms_huber the second part is summed as the perfect square (r_i / 2 alpha) |D x - (alpha / r_i) q|^2
+// where n <= alpha and r_i > 0; where r_i = 0 it is - <q, D x>, which is 0 for the q = 0 the dual kernel leaves.  fp64 throughout; the
+// per-site constants alpha / r_i ... are formed from g_i here (one division per column; the call runs once per convergence check).
+template <typename T, int V>
+__device__ __forceinline__ void gap_terms_hwtv(const Vec<T, V> (&o)[8], const Vec<T, V> (&qv)[8], const Vec<T, V>& xv, const Vec<T, V>& x0v,
+                                               const Vec<T, V>& gv, const Vec<T, V>& gd, double lambda, double alpha, double half_inv_alpha,
+                                               double& a_hwtv, double& a_fid, double& a_gap) {
+    const Vec<T, V> ds = sumsq_slots<T, V>(o);
+    auto column = [&]<int I>(IC<I>) {          // one column at a time, its index a compile-time constant (gap_terms_huber)
+        const double n = (double)tsqrt(ds.v[I]);
+        const double a = fmin(n, alpha);
+        const double h = (n - a) + (a * a) * half_inv_alpha;
+        const double r = lambda * (double)gv.v[I];
+        const double a_over_r = (r > 0.0) ? alpha / r : 0.0;
+        double sq = 0.0, dot = 0.0, qq = 0.0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {                                  // inactive slots are exactly zero in o and in qv
+            const double d = (double)o[c].v[I], qc = (double)qv[c].v[I];
+            const double e = d - a_over_r * qc;
+            sq += e * e;
+            dot += qc * d;
+            qq += qc * qc;
+        }
+        const double e = (double)xv.v[I] - (double)x0v.v[I];
+        const double rr = e + (double)gd.v[I];
+        a_hwtv += (double)gv.v[I] * h;
+        a_fid += 0.5 * e * e;
+        a_gap += 0.5 * rr * rr + ((r > 0.0 && n <= alpha) ? r * half_inv_alpha * sq : r * h - dot + 0.5 * a_over_r * qq);
+    };
+    [&]<int... I>(std::integer_sequence<int, I...>) { (column(IC<I>{}), ...); }(std::make_integer_sequence<int, V>{});
 }
 // D-side pass of the plane-marching form (k_D_march): |D x|_{2,1}, 1/2 |x - x0|^2 and sum (lambda |D x|_2 - <qs, D x>); reads x0 and q once.
 // The D^T-side pass (GapDT) ran BEFORE it on the same grid and left its per-block sums in `partials`: finish() adds to them.

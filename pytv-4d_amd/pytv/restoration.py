@@ -10,12 +10,12 @@ import math
 import torch
 
 from . import _native as _nv
-from .solvers import (AcceleratedChambollePock, AdaptiveTVChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock,
+from .solvers import (AcceleratedChambollePock, AdaptiveHuberChambollePock, AdaptiveTVChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock,
                       RobustChambollePock, WeightedChambollePock)
 from .tv_operators_GPU import _to_device
 
 __all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted", "denoise_tv_adaptive",
-           "edge_stopping_weights"]
+           "denoise_tv_adaptive_huber", "edge_stopping_weights"]
 
 
 def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
@@ -224,6 +224,39 @@ def denoise_tv_adaptive(image, weight=0.1, reg_weights=None, rel_gap=1e-4, max_n
             raise ValueError("denoise_tv_adaptive: reg_weights must have the shape of the image, %r (got %r)" % (tuple(x.shape), tuple(g.shape)))
         g = g.reshape(vol.shape)
     cp = AdaptiveTVChambollePock(vol, float(weight), g, scheme=scheme, reg_z_over_reg=1.0)
+    cp.run_until(rel_gap, max_num_iter, check_every)
+    out = cp.result().reshape(x.shape)
+    return out if was_torch else out.detach().cpu().numpy()
+
+
+def denoise_tv_adaptive_huber(image, weight=0.1, reg_weights=None, alpha=1.0, rel_gap=1e-4, max_num_iter=200, *, scheme="upwind", check_every=10):
+    """SPATIALLY ADAPTIVE HUBER-TV denoising of a 2-D (rows, cols) or 3-D (planes, rows, cols) image: minimises
+    1/2 |u - f|^2 + weight * sum_i reg_weights_i h_alpha(|grad u|_i) -- ``denoise_tv_adaptive`` with the Huber function of
+    ``denoise_tv_huber`` in place of the norm, so that the strongly smoothed flat and gently ramped regions do not come back as terraces.
+
+    weight      : denoising weight (larger = smoother), as in ``denoise_tv_chambolle``.
+    reg_weights : an array of the image's shape, finite and >= 0; None = all ones (``denoise_tv_huber``'s model).  Larger where the
+                  noise is stronger; ``edge_stopping_weights(image, kappa)`` to smooth less across edges; 0 inside a region that must be
+                  left as it is.
+    alpha       : the gradient magnitude, in grey levels per pixel, below which the model smooths quadratically; finite and > 0.
+    rel_gap     : stop when the duality gap certifies the answer, gap <= rel_gap * objective at a check
+                  (``AdaptiveHuberChambollePock.run_until``: 1/2 |u - u*|^2 <= gap), checked every ``check_every`` iterations, or after
+                  ``max_num_iter`` iterations.
+    The iterations take the solver's default path (``AdaptiveHuberChambollePock``: the kernel pair, or one sweep on large volumes in the
+    schemes where that measured faster).
+    Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point."""
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    vol = _as_volume(x, "denoise_tv_adaptive_huber")
+    if reg_weights is None:
+        g = torch.ones_like(vol)
+    else:
+        g = torch.as_tensor(reg_weights, device=x.device)
+        if tuple(g.shape) != tuple(x.shape):
+            raise ValueError("denoise_tv_adaptive_huber: reg_weights must have the shape of the image, %r (got %r)"
+                             % (tuple(x.shape), tuple(g.shape)))
+        g = g.reshape(vol.shape)
+    cp = AdaptiveHuberChambollePock(vol, float(weight), g, float(alpha), scheme=scheme, reg_z_over_reg=1.0)
     cp.run_until(rel_gap, max_num_iter, check_every)
     out = cp.result().reshape(x.shape)
     return out if was_torch else out.detach().cpu().numpy()

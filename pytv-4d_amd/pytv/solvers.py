@@ -23,6 +23,9 @@ fused HIP kernels (include/pytv4d.h):
     AdaptiveTVChambollePock  tv_cp_dual_wtv on the extrapolated point (projection onto a per-voxel radius reg * g_i, weighted TV partial)
                         (2Nd+2) + tv_cp_primal_accel with the accelerated schedule: spatially adaptive TV (noise-adaptive lambda,
                         edge-stopping weights, protected regions)
+    AdaptiveHuberChambollePock  tv_cp_dual_hwtv on the extrapolated point (per-voxel shrink and radius, weighted Huber partial) (2Nd+2) +
+                        tv_cp_primal_accel with fixed steps (or tv_cp_hwtv_sweep + tv_cp_accel_fixup: one sweep, 6+2Nd words/voxel +
+                        fix-up): the Huber-TV regulariser under a per-voxel weight, linearly convergent
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
     ADMM                tv_admm_tu / tv_admm_zu, tv_DT_axpy, tv_normal_op2 (I + rho D^T D from x alone, two dot products) +
                         tv_cg_update (single-reduction CG; textbook tv_cg_step1/2 kept)
@@ -42,7 +45,7 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "AdaptiveTVChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "AdaptiveTVChambollePock", "AdaptiveHuberChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
            "accel_schedule", "cp_linear_steps", "auto_pitch", "operator_norm_sq"]
 
 
@@ -1464,7 +1467,7 @@ class HuberChambollePock(_GapStopping, _OneSweepCP):
     Not built (out of scope here): the sweep / exchange / fix-up schedule of a sharded slab on the one-sweep path (slabs run the kernel
     pair), a persistent small-volume form, hipGraph capture, the placement tuner / arena of ``ChambollePock``, a plane-marching form of the
     gap kernel, and Huber-TV under the L1 / Huber / KL data terms of ``RobustChambollePock`` / ``PoissonChambollePock``.  A per-voxel
-    weight on the (plain) TV term is ``AdaptiveTVChambollePock``.
+    weight on the (plain) TV term is ``AdaptiveTVChambollePock``.  A per-voxel weight on THIS regulariser is ``AdaptiveHuberChambollePock``.
 
     Per-step scalars: the slots of ``ChambollePock`` -- sum h_alpha(|D x_bar|_2) in slot 0, 1/2 |x_new - x0|^2 in slot ``F`` (one-sweep
     path: the sweep's part in slot ``F``, the fix-up's in ``F + 1``; they are summed when the loss is asked for)."""
@@ -1559,6 +1562,7 @@ class AdaptiveTVChambollePock(AcceleratedChambollePock):
     persistent small-volume form, hipGraph capture, the placement tuner / arena of ``ChambollePock``, a plane-marching form of the gap
     kernel, g under the L1 / Huber / KL / weighted data terms of ``RobustChambollePock`` / ``PoissonChambollePock`` /
     ``WeightedChambollePock`` or with the Huber-TV regulariser of ``HuberChambollePock``, and g in ``ADMM`` / ``SubgradientDescent``.
+    g with the Huber-TV regulariser, one-sweep path included, is the sibling class ``AdaptiveHuberChambollePock``.
 
     Per-step scalars: the slots of ``ChambollePock`` -- sum g_i |D x_bar|_2 in slot 0, 1/2 |x_new - x0|^2 in slot ``F``."""
 
@@ -1622,6 +1626,126 @@ class AdaptiveTVChambollePock(AcceleratedChambollePock):
     duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
         calls; the state of the loop is not touched.  primal = 1/2 |x - x0|^2 + reg * sum g_i |D x|_2.  Sharded: collective, every rank
         calls it and gets the same numbers.
+        """, _GAP_DOC)
+    run_until = _redoc(_GapStopping.run_until, tail=_GAP_DOC)
+
+
+# =================================================================================================
+class AdaptiveHuberChambollePock(_GapStopping, _OneSweepCP):
+    """min_x 1/2 |x - x0|^2 + regularization * sum_i g_i h_alpha(|D x|_{2,i}) -- the HUBER-TV regulariser of ``HuberChambollePock`` under the
+    PER-VOXEL WEIGHT g_i >= 0 of ``AdaptiveTVChambollePock`` (``reg_weights``, an array like x0).  Edge-stopping weights and noise-adaptive
+    lambda smooth hardest on the flat and gently ramped regions, exactly where plain TV leaves terraces; h_alpha is quadratic below the
+    gradient magnitude ``alpha`` and removes them (see the two sibling classes for what g and alpha mean).
+
+    With r_i = reg g_i the conjugate of a site's term is alpha |q_i|^2 / (2 r_i) + indicator(|q_i|_2 <= r_i) (g_i = 0: the indicator of
+    q_i = 0); it is (alpha / (reg g_max))-strongly convex, the fidelity is 1-strongly convex, so Algorithm 3 of Chambolle & Pock 2011
+    applies: FIXED steps from ``cp_linear_steps(L2, gamma, alpha / (reg g_max))``, linear convergence.  g_max is the maximum of g over ALL
+    ranks, so every rank takes the same steps; an all-zero g is allowed (g_max = 1 for the steps) and the solver then returns x0.  State:
+    x, x_bar (images), q (gradient); x = x_bar = x0, q = 0 at the start.  One iteration:
+
+        shrink_i = r_i / (r_i + sigma alpha)                                        (0 where r_i = 0)
+        v      = shrink_i (q + sigma D x_bar)
+        q     <- v where |v|_2 <= r_i, v r_i / |v|_2 beyond, 0 where r_i = 0        tv_cp_dual_hwtv on x_bar   (2 Nd + 2 words per voxel)
+        x_new <- (x - tau D^T q + tau x0) / (1 + tau)
+        x_bar <- x_new + theta (x_new - x);  x <- x_new                             tv_cp_primal_accel, one pass (Nd + 4)
+
+    -- 3 Nd + 6 words per voxel as that kernel pair.  A site inside its ball keeps v bit for bit and a site with g_i = 0 keeps q = 0
+    exactly, so a protected voxel whose neighbouring sites are protected too never moves.  g is stored like x0 (this rank's planes, pitched
+    with it) and needs no halo plane.  Sharded (``slab``): the kernel pair, the boundary plane(s) of x_bar travel before the dual kernel and
+    those of q before the primal kernel, both waits exposed.
+
+    The ONE-SWEEP path (``set_fused``, ``fused``) runs the same iteration as tv_cp_hwtv_sweep + tv_cp_accel_fixup -- the one-sweep kernel of
+    ``HuberChambollePock`` with g of the site as one more streamed load per frame; the fix-up is ``AcceleratedChambollePock``'s, unchanged:
+    2 Nd + 6 words per voxel.  The state (x, x_bar, q) is the same on both paths, so ``set_fused`` may be called between iterations at any
+    time.  DEFAULT: ``ChambollePock``'s rule -- the sweep where tv_cp_fused_supported accepts the geometry, the volume is not sharded and
+    holds at least 1024 * TV_FUSED_MIN_KVOXELS (16 Mi) voxels -- but only for the schemes in ``SWEEP_DEFAULT_SCHEMES``, those whose sweep
+    iteration measured faster than the pair's by more than the pair's run-to-run spread on 64x8x1024x1024 fp32
+    (profiles/adaptive_huber_bench.txt); the pair otherwise.
+
+    The model has an EXACT duality gap (tv_dual_gap_hwtv), so ``duality_gap`` / ``run_until`` certify the iterate.
+
+    Not built (out of scope here): a plane-marching form of the dual kernel (large-plane SLABS run the one-site kernel; unsharded large
+    planes have the sweep) and of the gap kernel, the sweep / exchange / fix-up schedule of a sharded slab, a persistent small-volume form,
+    hipGraph capture, and a per-voxel alpha.
+
+    Per-step scalars: the slots of ``ChambollePock`` -- sum g_i h_alpha(|D x_bar|_2) in slot 0, 1/2 |x_new - x0|^2 in slot ``F`` (one-sweep
+    path: the sweep's part in slot ``F``, the fix-up's in ``F + 1``; they are summed when the loss is asked for)."""
+
+    SWEEP_DEFAULT_SCHEMES = ("upwind", "downwind", "hybrid")      # not central: its sweep took 1.08 of the pair's time (it runs without the dual prefetch)
+
+    def _one_sweep_default(self, sharded_ok):
+        """``_SlabProblem``'s rule, for the schemes in ``SWEEP_DEFAULT_SCHEMES`` only (class docstring)"""
+        return self.scheme in self.SWEEP_DEFAULT_SCHEMES and super()._one_sweep_default(sharded_ok)
+
+    def __init__(self, x0, regularization, reg_weights, alpha, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False,
+                 factor_reg_static=0, gamma=1.0, slab=None, pitch="auto"):
+        """reg_weights: g, a floating-point (or bool) array of x0's shape (this rank's slab), finite and >= 0; kept in the layout of x0.
+        alpha, regularization: finite and > 0.  gamma: as in ``HuberChambollePock``, 0 < gamma <= 1.  ValueError otherwise; sharded: the
+        check of g is collective, every rank raises.  pitch: see ``_SlabProblem``.  The path of the iterations starts at the default rule
+        of the class docstring; ``set_fused`` changes it."""
+        alpha, gamma = float(alpha), float(gamma)
+        if not (math.isfinite(alpha) and alpha > 0.0):
+            raise ValueError("AdaptiveHuberChambollePock: alpha must be finite and > 0 (alpha = 0 is plain adaptive TV: AdaptiveTVChambollePock)")
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError("AdaptiveHuberChambollePock: gamma must be in (0, 1]")
+        if not (math.isfinite(float(regularization)) and float(regularization) > 0.0):
+            raise ValueError("AdaptiveHuberChambollePock: regularization must be finite and > 0")
+        # g is checked BEFORE the state is allocated (an x0 that is no device tensor is left to the base's own refusal)
+        g = None
+        if isinstance(x0, torch.Tensor) and x0.is_cuda:
+            try:
+                g = AdaptiveTVChambollePock._checked_weights(x0, reg_weights, slab)
+            except ValueError as exc:            # the sibling's check (collective on slabs), under this class's name
+                raise ValueError(str(exc).replace("AdaptiveTVChambollePock", "AdaptiveHuberChambollePock", 1)) from None
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, slab, pitch)
+        gmax = g.max().to(torch.float64).reshape(1)
+        self.slab.allreduce_max_(gmax)                    # over ALL ranks: the steps must be the same everywhere
+        self.g_max = float(gmax.item())
+        self.alpha, self.gamma = alpha, gamma
+        self.tau, self.sigma, self.theta, self.mu = cp_linear_steps(self.L2, gamma, alpha / (self.reg * (self.g_max if self.g_max > 0.0 else 1.0)))
+        self._alloc_state()
+        self.g = self.image_copy(g)
+        self._init_path()
+
+    fused = property(_OneSweepCP.fused.fget, doc="True: iterations run as tv_cp_hwtv_sweep + tv_cp_accel_fixup; False: as tv_cp_dual_hwtv + "
+                                                 "tv_cp_primal_accel (``set_fused``)")
+
+    def _dual_kernel(self, sigma, out_ptr):
+        _nv.check(self.lib.tv_cp_dual_hwtv(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
+                                           _nv.ptr(self.g), sigma, self.reg, self.alpha, out_ptr, _nv.ptr(self.ws), self.stream))
+
+    def _sweep_kernel(self, tau, sigma, theta, tv_ptr, fid_ptr, g, ws, st):
+        _nv.check(self.lib.tv_cp_hwtv_sweep(g, _nv.ptr(self.x_bar), None, None, _nv.ptr(self.q), _nv.ptr(self.q), _nv.ptr(self.x0),
+                                            _nv.ptr(self.x), _nv.ptr(self.x_bar_alt), _nv.ptr(self.g), sigma, self.reg, self.alpha, tau,
+                                            theta, 0, 0, -1, tv_ptr, fid_ptr, ws, st))
+
+    step = _redoc(_ExtrapolatedCP.step, """Enqueue one iteration.  out: fp64 device tensor of SLOTS words (zero on entry) receiving this rank's sum g_i h_alpha(|D x_bar|_2)
+        in slot 0 and 1/2 |x_new - x0|^2 in slot F; defaults to an internal scratch.""")
+
+    def run(self, n_iter, record_loss=True):
+        """n_iter iterations (one host synchronisation at the end); returns the loss history as a numpy array (global over all ranks), or
+        None.  Row k is 1/2 |x_{k+1} - x0|^2 + reg * sum g_i h_alpha(|D x_bar_k|_2): the regulariser is that of the EXTRAPOLATED point the
+        dual step saw -- a progress indicator in the slots of ``ChambollePock``'s history.  The exact primal value of the current iterate
+        is ``duality_gap()[0]``."""
+        return self._run(n_iter, record_loss)
+
+    _GAP_DOC = """For P(x) = 1/2 |x - x0|^2 + reg sum g_i h_alpha(|D x|_{2,i}) and any dual variable q with |q|_2 <= r_i = reg g_i per site,
+        Dual(q) = <D^T q, x0> - 1/2 |D^T q|^2 - sum_{r_i > 0} alpha |q_i|^2 / (2 r_i) <= P(x*) <= P(x), and by strong convexity
+        1/2 |x - x*|^2 <= P(x) - Dual(q).  The kernel (tv_dual_gap_hwtv) sums the gap site by site as 1/2 (x - x0 + D^T q)^2 +
+        [r_i h_alpha(|D x|_2) + alpha |q|^2 / (2 r_i) - <q, D x>], both parts >= 0 (the second as a perfect square where |D x|_2 <= alpha),
+        and writes nothing but three scalars.
+        fp32 FLOOR: beyond alpha the second part cancels, leaving an absolute error of order eps_fp32 * P, so relative gaps below about 1e-6
+        are not resolvable in fp32; the gap may then come out slightly negative (it is not clamped) and ``run_until`` ends on its iteration
+        limit with ``converged=False``."""
+
+    def _gap_kernel(self, x, q, qscale, b, out):
+        _nv.check(self.lib.tv_dual_gap_hwtv(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]),
+                                            _nv.ptr(b["qn"]), _nv.ptr(self.x0), _nv.ptr(self.g), self.reg, self.alpha, out.data_ptr(),
+                                            _nv.ptr(self.ws), self.stream))
+
+    duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+        calls; the state of the loop is not touched.  primal = 1/2 |x - x0|^2 + reg * sum g_i h_alpha(|D x|_2).  Sharded: collective, every
+        rank calls it and gets the same numbers.
         """, _GAP_DOC)
     run_until = _redoc(_GapStopping.run_until, tail=_GAP_DOC)
 

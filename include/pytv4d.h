@@ -410,6 +410,46 @@ int tv_cp_dual_hwtv(const tv_geom* g, const void* x, const void* x_prev, const v
 int tv_dual_gap_hwtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
                      const void* q_next, const void* x0, const void* gw, double lambda, double alpha, double* out, void* ws, void* stream);
 
+/* Dual step of Chambolle-Pock for the CHANNEL-COUPLED (vectorial / joint / collaborative) TV regulariser: the M frames of the volume are
+ * channels of ONE object (dual- and multi-energy CT, multi-contrast or multi-echo series, colour stacks, gated frames with shared anatomy)
+ * and one Frobenius norm is taken per SPATIAL site s = (z, y, x) over all Nd gradient channels c and all M frames m,
+ *   P(x) = 1/2 |x - x0|^2 + lambda sum_s |D x|_{F,s},    |D x|_{F,s} = ( sum_{m,c} (D x)[z, c, m, y, x]^2 )^(1/2).
+ * With reg_time = 0 this is the pure spatial joint TV; with reg_time > 0 the weighted time differences join the same norm; M = 1 is plain
+ * TV.  The conjugate is the indicator of one ball of radius lambda per spatial site bounding the M Nd-vector.  At each site
+ *   v = q + sigma_D D x for every frame and channel,  n = |v|_{F,s};   q <- v where n <= lambda,  v * (lambda / n) beyond
+ * with ONE FACTOR PER SITE, selected (the constant 1, or lambda / n) and applied to every frame and channel of the site.
+ *   *vtv (device fp64) = sum_s |D x|_{F,s} of the local planes, accumulated in fp64: the loss is fid + lambda * *vtv.
+ * EXACT, for finite inputs: a site inside its ball keeps q = v bit for bit (v times the constant 1; v is formed as tv_cp_dual_wtv forms
+ * it); lambda / n is evaluated only where n > lambda > 0, so the result is never NaN or Inf; |q_s|_F <= lambda up to rounding afterwards.
+ * A thread owns one spatial site and walks its frames.  Two kernel forms, chosen by (scheme, M):
+ *   register form  M <= 8 (hybrid: M <= 4): v of all frames stays in registers, x and q are read once and q is written once: 2 Nd + 1 words per voxel
+ *   generic form   any M:  pass 1 accumulates n^2 over the frames, pass 2 recomputes v and stores v * factor: 3 Nd + 2 words per voxel if
+ *                  pass 2 is served by HBM alone, less where L2 / MALL hold the site's frames.  v is never written unscaled.
+ * (option TV_VTV_FORM = 2: the generic form for every M; the two forms give the same q bit for bit.)  q is written in place, nothing else but vtv and ws.  x_prev / x_next,
+ * alignment and geometries as tv_cp_dual: four schemes, fp32 / fp64, 16-byte lanes or scalar rows, pitched arrays, mask_static /
+ * time_factor / time_weight_vol, z-slabs (a z-cut never separates the frames of a site).  There is no plane-marching form.  The primal half
+ * of the iteration is tv_cp_primal_accel.
+ * TV_E_ARG: a NULL array ("<name> is NULL"), lambda or sigma_D not finite and > 0, a tv_geom of another interface version; a missing halo
+ * plane is TV_E_HALO ("x_prev: ..." / "x_next: ..."); all checks precede any device access. */
+int tv_cp_dual_vtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, void* q,
+                   double sigma_D, double lambda, double* vtv, void* ws, void* stream);
+
+/* Duality-gap certificate of the channel-coupled model above for an iterate x and a dual variable q with |q_s|_F <= lambda per spatial
+ * site (what tv_cp_dual_vtv leaves).  Dual(q) = <gd, x0> - 1/2 |gd|^2 with gd = D^T q.  Over the local planes
+ *   out[0] = sum_s |D x|_{F,s}
+ *   out[1] = 1/2 |x - x0|^2
+ *   out[2] = sum_voxels 1/2 (x - x0 + gd)^2  +  sum_s ( lambda |D x|_{F,s} - sum_{m,c} q D x )  =  P(x) - Dual(q)
+ * EXACT for any feasible q.  Both parts are >= 0 site by site (Cauchy-Schwarz over the joint vector); they are accumulated in that form in
+ * fp64 (a site's |D x|^2 and <q, D x> are summed over its frames in fp64 from the stencil's results), never as P - Dual, not clamped.
+ * The caller has P = out[1] + lambda * out[0], Dual = P - out[2], and 1/2 |x - x*|^2 <= out[2].
+ * REDUCE-ONLY: nothing is written except out (three device fp64 words) and ws.  x_prev / x_next as in tv_cp_dual, q_prev / q_next as in
+ * tv_dual_gap; slab partials add up to the unsharded scalars.  One kernel form for every geometry of tv_cp_dual_vtv (a thread owns a spatial
+ * site and walks its frames; Nd + 2 words per voxel): the call is made once per convergence check.
+ * TV_E_ARG: a NULL array ("<name> is NULL"), lambda not finite and > 0, a tv_geom of another interface version; a missing halo plane is
+ * TV_E_HALO ("x_prev: ..." / "x_next: ..." / "q_prev: ..." / "q_next: ..."); all checks precede any device access. */
+int tv_dual_gap_vtv(const tv_geom* g, const void* x, const void* x_prev, const void* x_next, const void* q, const void* q_prev,
+                    const void* q_next, const void* x0, double lambda, double* out, void* ws, void* stream);
+
 /* One-sweep form of the same iteration (all four schemes; fp32, nx % 4 == 0, nx >= 64,
  * any m: more than 8 frames are processed as time windows of 8): q is read and written ONCE per
  * iteration.  x is ping-ponged.

@@ -7,6 +7,7 @@
 //   g_options, env_int           the option table
 //   plane_big_enough, march_ok   which kernel family a geometry takes
 //   check_x_halos[2], check_y_halos   halo rules
+//   wtv_null, wtv_halo           argument / halo errors that start with the argument's name
 //   finite_pos, finite_in_01     scalar rules
 //   Call, pick_store             one D / D^T launch; run-time store flag -> epilogue template
 //   namespace tvm                launchers defined in the other translation units
@@ -238,7 +239,7 @@ inline TvOption g_options[] = {
     {"TV_NO_MARCH_SUBGRAD", 0, 0}, {"TV_NO_MARCH_NORMAL", 0, 0}, {"TV_SCALAR_GATHER", 0, 0}, {"TV_NO_FUSED", 0, 0},
     {"TV_NO_FUSED_TWIN", 0, 0}, {"TV_FUSED_XW", 0, 0}, {"TV_FUSED_FORCE_TWIN", 0, 0}, {"TV_NO_FUSED_SUBGRAD", 0, 0},
     {"TV_NORMAL_KERNEL", 0, 0}, {"TV_D_KERNEL", 0, 0}, {"TV_DT_KERNEL", 0, 0}, {"TV_FUSED_MIN_KVOXELS", 0, 0}, {"TV_SG_KERNEL", 0, 0}, {"TV_SPARE", 0, 0}, {"TV_SG_ALIGNED", 0, 0},
-    {"TV_SMALL_MAX_KVOXELS", 0, 0}, {"TV_NO_SMALL", 0, 0}, {"TV_SMALL_BLOCKS_PER_CU", 0, 0}, {"TV_SMALL_GENERIC", 0, 0}, {"TV_SMALL_TILES", 0, 0}, {"TV_SMALL_SITES", 0, 0}, {"TV_NS_NO_FIRST", 0, 0},
+    {"TV_SMALL_MAX_KVOXELS", 0, 0}, {"TV_NO_SMALL", 0, 0}, {"TV_SMALL_BLOCKS_PER_CU", 0, 0}, {"TV_SMALL_GENERIC", 0, 0}, {"TV_SMALL_TILES", 0, 0}, {"TV_SMALL_SITES", 0, 0}, {"TV_NS_NO_FIRST", 0, 0}, {"TV_VTV_FORM", 0, 0},
 };
 inline std::once_flag g_options_once;
 inline TvOption* find_option(const char* name) {
@@ -329,6 +330,21 @@ inline int check_y_halos(const tv_geom* g, const DG& d, const void* yp, const vo
     if (need_prev && g->z0 > 0 && yp == nullptr) return fail(TV_E_HALO, "previous-slab gradient halo required");
     if (need_next && g->z0 + g->nz < g->nz_global && yn == nullptr) return fail(TV_E_HALO, "next-slab gradient halo required");
     return 0;
+}
+
+// Argument checks of the entry points that name the offending argument (tv_cp_dual_wtv and the entry points added after it): each text starts with the name of the offending argument.
+inline int wtv_null(std::initializer_list<std::pair<const char*, const void*>> ps) {
+    for (const auto& p : ps)
+        if (p.second == nullptr) {
+            g_err = std::string(p.first) + " is NULL";
+            return TV_E_ARG;
+        }
+    return 0;
+}
+// a halo check of tv_host.h with the missing argument's name in front of its text (which begins "previous-slab" or "next-slab")
+inline int wtv_halo(int rc, const char* prev, const char* next) {
+    if (rc) g_err = std::string(g_err.rfind("previous", 0) == 0 ? prev : next) + ": " + g_err;
+    return rc;
 }
 
 // ---- plane-marching launchers, defined in tv_march_D.hip / tv_march_DT.hip ---------------------------

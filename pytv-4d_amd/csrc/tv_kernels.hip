@@ -1114,21 +1114,6 @@ int tv_cp_dual_huber(const tv_geom* g, const void* x, const void* x_prev, const 
     }, P, hubout);
 }
 
-// Argument checks of the two spatially adaptive entry points: each text starts with the name of the offending argument.
-static int wtv_null(std::initializer_list<std::pair<const char*, const void*>> ps) {
-    for (const auto& p : ps)
-        if (p.second == nullptr) {
-            g_err = std::string(p.first) + " is NULL";
-            return TV_E_ARG;
-        }
-    return 0;
-}
-// a halo check of tv_host.h with the missing argument's name in front of its text (which begins "previous-slab" or "next-slab")
-static int wtv_halo(int rc, const char* prev, const char* next) {
-    if (rc) g_err = std::string(g_err.rfind("previous", 0) == 0 ? prev : next) + ": " + g_err;
-    return rc;
-}
-
 // Dual step for the spatially adaptive regulariser lambda sum g_i |D x|_2 (include/pytv4d.h): tv_cp_dual's halo, alignment and launch rules
 // with the CpDualWtv epilogue, which reads one more array (gw, stored like an image: no halo plane).  Every argument check precedes the
 // first device access.  Marching: not where wtv_spill16(scheme, M) (tv_host.h): the one-site kernel runs there.

@@ -23,10 +23,10 @@ from . import slab               # noqa: E402
 from . import restoration        # noqa: E402
 from . import utils              # noqa: E402
 from .restoration import (denoise_tv_adaptive, denoise_tv_adaptive_huber, denoise_tv_chambolle, denoise_tv_huber, denoise_tv_poisson, denoise_tv_robust,   # noqa: E402
-                          denoise_tv_weighted, edge_stopping_weights)
+                          denoise_tv_vectorial, denoise_tv_weighted, edge_stopping_weights)
 
 __all__ = ["tv_GPU", "tv_operators_GPU", "solvers", "slab", "restoration", "utils", "denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted",
-           "denoise_tv_adaptive", "edge_stopping_weights", "denoise_tv_adaptive_huber"]
+           "denoise_tv_adaptive", "edge_stopping_weights", "denoise_tv_adaptive_huber", "denoise_tv_vectorial"]
 
 
 def __getattr__(name):

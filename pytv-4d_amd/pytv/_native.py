@@ -101,6 +101,8 @@ _SIGNATURES = {
     "tv_dual_gap_wtv": (ctypes.c_int, [_G] + [_c_void_p] * 8 + [ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_dual_hwtv": (ctypes.c_int, [_G] + [_c_void_p] * 5 + [ctypes.c_double] * 3 + [_c_double_p, _c_void_p, _c_void_p]),
     "tv_dual_gap_hwtv": (ctypes.c_int, [_G] + [_c_void_p] * 8 + [ctypes.c_double] * 2 + [_c_double_p, _c_void_p, _c_void_p]),
+    "tv_cp_dual_vtv": (ctypes.c_int, [_G] + [_c_void_p] * 4 + [ctypes.c_double] * 2 + [_c_double_p, _c_void_p, _c_void_p]),
+    "tv_dual_gap_vtv": (ctypes.c_int, [_G] + [_c_void_p] * 7 + [ctypes.c_double, _c_double_p, _c_void_p, _c_void_p]),
     "tv_cp_fused_supported": (ctypes.c_int, [_G]),
     "tv_cp_zchunk": (ctypes.c_int, [_G]),
     "tv_cp_fused": (ctypes.c_int, [_G] + [_c_void_p] * 7 + [ctypes.c_double] * 4 + [ctypes.c_int64] * 2 + [_c_double_p] * 2

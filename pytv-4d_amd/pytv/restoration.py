@@ -11,11 +11,11 @@ import torch
 
 from . import _native as _nv
 from .solvers import (AcceleratedChambollePock, AdaptiveHuberChambollePock, AdaptiveTVChambollePock, ChambollePock, HuberChambollePock, PoissonChambollePock,
-                      RobustChambollePock, WeightedChambollePock)
+                      RobustChambollePock, VectorialTVChambollePock, WeightedChambollePock)
 from .tv_operators_GPU import _to_device
 
 __all__ = ["denoise_tv_chambolle", "denoise_tv_robust", "denoise_tv_poisson", "denoise_tv_huber", "denoise_tv_weighted", "denoise_tv_adaptive",
-           "denoise_tv_adaptive_huber", "edge_stopping_weights"]
+           "denoise_tv_adaptive_huber", "edge_stopping_weights", "denoise_tv_vectorial"]
 
 
 def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, *, scheme="upwind", check_every=10, rel_gap=None,
@@ -259,4 +259,34 @@ def denoise_tv_adaptive_huber(image, weight=0.1, reg_weights=None, alpha=1.0, re
     cp = AdaptiveHuberChambollePock(vol, float(weight), g, float(alpha), scheme=scheme, reg_z_over_reg=1.0)
     cp.run_until(rel_gap, max_num_iter, check_every)
     out = cp.result().reshape(x.shape)
+    return out if was_torch else out.detach().cpu().numpy()
+
+
+def denoise_tv_vectorial(image, weight=0.1, channel_axis=0, rel_gap=1e-4, max_num_iter=200, *, scheme="upwind", check_every=10):
+    """CHANNEL-COUPLED (vectorial / joint) total-variation denoising of a multi-channel image: minimises
+    1/2 |u - f|^2 + weight * sum_pixels ( sum_channels |grad u_c|^2 )^(1/2) -- one norm per pixel over ALL channels, so the channels keep
+    their edges in the same places (colour images, dual- and multi-energy or multi-contrast stacks).
+
+    image        : 3-D, channels along ``channel_axis`` and (rows, cols) in the remaining order -- (C, H, W) for ``channel_axis`` 0,
+                   (H, W, C) for -1 --, or 4-D with planes as well: (Nz, C, H, W) after moving ``channel_axis`` to position 1.
+                   ValueError for any other rank.
+    weight       : denoising weight (larger = smoother), as in ``denoise_tv_chambolle``.  One channel is ``denoise_tv_chambolle``'s model.
+    channel_axis : the axis of ``image`` that holds the channels (0 for 3-D input means (C, H, W); for 4-D input the planes are the first
+                   of the remaining axes).
+    rel_gap      : stop when the duality gap certifies the answer, gap <= rel_gap * objective at a check
+                   (``VectorialTVChambollePock.run_until``: 1/2 |u - u*|^2 <= gap), checked every ``check_every`` iterations, or after
+                   ``max_num_iter`` iterations.
+    Returns an array of the input's kind (numpy in -> numpy out, torch in -> device tensor), floating point, with the input's shape and
+    axis order."""
+    was_torch = isinstance(image, torch.Tensor)
+    x, _ = _to_device(image)
+    if x.dim() not in (3, 4):
+        raise ValueError("denoise_tv_vectorial: 3-D (channels, rows, cols) or 4-D (planes, channels, rows, cols) images only, "
+                         "with the channels along channel_axis")
+    moved = torch.movedim(x, channel_axis, 0 if x.dim() == 3 else 1)
+    vol = (moved.unsqueeze(0) if x.dim() == 3 else moved).contiguous()
+    cp = VectorialTVChambollePock(vol, float(weight), scheme=scheme, reg_z_over_reg=1.0)
+    cp.run_until(rel_gap, max_num_iter, check_every)
+    out = cp.result().reshape(moved.shape)
+    out = torch.movedim(out, 0 if x.dim() == 3 else 1, channel_axis).contiguous()
     return out if was_torch else out.detach().cpu().numpy()

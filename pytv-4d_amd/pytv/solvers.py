@@ -26,6 +26,9 @@ fused HIP kernels (include/pytv4d.h):
     AdaptiveHuberChambollePock  tv_cp_dual_hwtv on the extrapolated point (per-voxel shrink and radius, weighted Huber partial) (2Nd+2) +
                         tv_cp_primal_accel with fixed steps (or tv_cp_hwtv_sweep + tv_cp_accel_fixup: one sweep, 6+2Nd words/voxel +
                         fix-up): the Huber-TV regulariser under a per-voxel weight, linearly convergent
+    VectorialTVChambollePock  tv_cp_dual_vtv on the extrapolated point (ONE projection per spatial site over all frames and channels: a
+                        thread walks the frames of its site) (2Nd+1 up to 8 frames, hybrid 4; at most 3Nd+2 beyond) + tv_cp_primal_accel with the
+                        accelerated schedule: channel-coupled (vectorial / joint) TV of multi-energy, multi-contrast and colour stacks
     ChambollePockOperator  the same with a user data-fidelity operator A / A^T on device tensors (tv_cp_dual + tv_cpop_*)
     ADMM                tv_admm_tu / tv_admm_zu, tv_DT_axpy, tv_normal_op2 (I + rho D^T D from x alone, two dot products) +
                         tv_cg_update (single-reduction CG; textbook tv_cg_step1/2 kept)
@@ -45,7 +48,7 @@ import torch
 from . import _native as _nv
 from .slab import HaloPlan, Slab
 
-__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "AdaptiveTVChambollePock", "AdaptiveHuberChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
+__all__ = ["ChambollePock", "AcceleratedChambollePock", "RobustChambollePock", "PoissonChambollePock", "WeightedChambollePock", "HuberChambollePock", "AdaptiveTVChambollePock", "AdaptiveHuberChambollePock", "VectorialTVChambollePock", "ChambollePockOperator", "ADMM", "SubgradientDescent", "cp_step_size", "cp_step_pair",
            "accel_schedule", "cp_linear_steps", "auto_pitch", "operator_norm_sq"]
 
 
@@ -675,7 +678,7 @@ class _SlabProblem:
 
 class _GapStopping:
     """``duality_gap`` / ``run_until`` of the solvers whose state (x, q) carries an exact duality gap (``ChambollePock``,
-    ``AcceleratedChambollePock``, ``HuberChambollePock``, ``AdaptiveTVChambollePock``), over ``_gap_certificate`` / ``_run_until_gap`` of
+    ``AcceleratedChambollePock``, ``HuberChambollePock``, ``AdaptiveTVChambollePock``, ``VectorialTVChambollePock``), over ``_gap_certificate`` / ``_run_until_gap`` of
     ``_SlabProblem``.  A class binds the two under its own text with ``_redoc``: the ``_GAP_DOC`` of its model as the tail (a head of its
     own where it says more) and supplies ``_gap_kernel`` where its gap is not plain TV's."""
 
@@ -1214,7 +1217,7 @@ class _ExtrapolatedCP(_SlabProblem):
         _steps(k)                           (tau, sigma, theta) of iteration k as Python floats.  Here: the constants ``self.tau``,
                                             ``self.sigma``, ``self.theta`` (Algorithm 1: theta = 1; Algorithm 3: ``cp_linear_steps``);
                                             ``AcceleratedChambollePock``: the schedule of Algorithm 2
-        _dual_kernel(sigma, out_ptr)        here tv_cp_dual (plain TV); tv_cp_dual_huber, tv_cp_dual_wtv
+        _dual_kernel(sigma, out_ptr)        here tv_cp_dual (plain TV); tv_cp_dual_huber, tv_cp_dual_wtv, tv_cp_dual_vtv
         _primal_kernel(tau, theta, out_ptr) here tv_cp_primal_accel (quadratic fidelity); ``_FixedPointResiduals``: the class's ``_prox``
 
     and keeps ``step`` / ``run`` under docstrings of its own (what its scalars mean).  The one-sweep form of the iteration is
@@ -1371,7 +1374,8 @@ class AcceleratedChambollePock(_GapStopping, _OneSweepCP):
     (slabs run the kernel pair) -- at the reference's small shapes the solver pays a launch per kernel against the persistent loop of
     ``ChambollePock`` (DESIGN.md section 3.4).  The Huber-TV regulariser (quadratic below a gradient magnitude alpha, against staircasing;
     linearly convergent) is ``HuberChambollePock``; a per-voxel weight on the TV term (spatially adaptive TV, this schedule) is
-    ``AdaptiveTVChambollePock``.
+    ``AdaptiveTVChambollePock``; one norm per spatial site over all frames (channel-coupled TV, this schedule) is
+    ``VectorialTVChambollePock``.
 
     gamma = 0 gives theta = 1 and constant steps (Algorithm 1 with extrapolation).  The step schedule continues across ``run`` /
     ``run_steps`` / ``step`` calls (``self.it`` counts the iterations done); ``reset()`` starts it again.
@@ -1625,6 +1629,80 @@ class AdaptiveTVChambollePock(AcceleratedChambollePock):
 
     duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
         calls; the state of the loop is not touched.  primal = 1/2 |x - x0|^2 + reg * sum g_i |D x|_2.  Sharded: collective, every rank
+        calls it and gets the same numbers.
+        """, _GAP_DOC)
+    run_until = _redoc(_GapStopping.run_until, tail=_GAP_DOC)
+
+
+# =================================================================================================
+class VectorialTVChambollePock(AcceleratedChambollePock):
+    """min_x 1/2 |x - x0|^2 + regularization * sum_s |D x|_{F,s} -- CHANNEL-COUPLED (vectorial / joint / collaborative) TV: the M frames of
+    the (Nz, M, N, N) volume are channels of ONE object, and one Frobenius norm is taken per SPATIAL site s = (z, y, x) over all gradient
+    channels c and all frames m,
+
+        |D x|_{F,s} = ( sum_{m,c} (D x)[z, c, m, y, x]^2 )^(1/2)
+
+    (Blomgren & Chan 1998; Bresson & Chan 2008).  Every other solver here regularises the frames independently -- their edges move
+    independently and detail is lost in the weak channels; the coupled norm puts the edges of all channels in the same places: dual- and
+    multi-energy CT, multi-contrast or multi-echo series, colour stacks, gated frames with shared anatomy.  With ``reg_time`` = 0 this is
+    the pure spatial joint TV; with ``reg_time`` > 0 the weighted time differences join the same norm; M = 1 is plain TV.
+
+    The fidelity is still 1-strongly convex and |D|^2 is unchanged, so the iteration is that of ``AcceleratedChambollePock`` (Chambolle &
+    Pock 2011, Algorithm 2, ``accel_schedule``); only the ball of the dual projection changes -- ONE ball of radius reg per spatial site
+    bounding the M Nd-vector, so ONE factor per site, applied to every frame and channel.  Iteration k:
+
+        v      = q + sigma_k D x_bar  (all m, c of site s);  n_s = |v_s|_F
+        q     <- v where n_s <= reg, v reg / n_s beyond                             tv_cp_dual_vtv on x_bar
+        x_new <- (x - tau_k D^T q + tau_k x0) / (1 + tau_k)
+        x_bar <- x_new + theta_k (x_new - x);  x <- x_new                           tv_cp_primal_accel, one pass (Nd + 4)
+
+    tv_cp_dual_vtv: a thread owns a spatial site and walks its frames.  Up to 8 frames (hybrid: 4) v stays in registers -- 2 Nd + 1 words
+    per voxel, the pair moves the 3 Nd + 5 words of ``AcceleratedChambollePock``'s; more frames take two passes over the site's frames (n_s,
+    then v again times the factor): at most 3 Nd + 2, so 4 Nd + 6 words for the pair, less where the caches hold a site's frames (DESIGN.md
+    section 3.11).  A site inside its ball keeps v bit for bit; nothing is NaN or Inf for finite input.  Sharded (``slab``): as
+    ``AcceleratedChambollePock`` -- a z-cut never separates the frames of a site, so the same kernel pair runs with the same exchanges.
+
+    The model has an EXACT duality gap (tv_dual_gap_vtv), so ``duality_gap`` / ``run_until`` certify the iterate as they do for plain TV.
+
+    Not built (out of scope here): a one-sweep / fix-up, plane-marching, persistent or hipGraph form of the iteration (``set_fused(True)``
+    raises, ``fused`` is always False), a per-voxel weight or the Huber function on the coupled norm (``AdaptiveTVChambollePock`` /
+    ``HuberChambollePock`` have them per frame), and the coupled norm in ``ADMM`` / ``SubgradientDescent``.
+
+    Per-step scalars: the slots of ``ChambollePock`` -- sum_s |D x_bar|_{F,s} in slot 0, 1/2 |x_new - x0|^2 in slot ``F``."""
+
+    def __init__(self, x0, regularization, scheme="hybrid", reg_z_over_reg=1.0, reg_time=0.0, mask_static=False, factor_reg_static=0,
+                 tau0=None, sigma0=None, gamma=1.0, slab=None, pitch="auto"):
+        """regularization: finite and > 0 (ValueError otherwise).  tau0, sigma0, gamma, pitch: see ``AcceleratedChambollePock``."""
+        if not (math.isfinite(float(regularization)) and float(regularization) > 0.0):
+            raise ValueError("VectorialTVChambollePock: regularization must be finite and > 0")
+        super().__init__(x0, regularization, scheme, reg_z_over_reg, reg_time, mask_static, factor_reg_static, tau0, sigma0, gamma, slab, pitch)
+
+    def set_fused(self, fused):
+        """The one-sweep kernels project frame by frame: True raises ValueError; False and None (the construction default) keep the kernel
+        pair.  ``fused`` is always False."""
+        if fused:
+            raise ValueError("set_fused(True): VectorialTVChambollePock has no one-sweep path (the one-sweep kernels project each frame's "
+                             "dual vector on its own)")
+        self._fused = False
+
+    def _dual_kernel(self, sigma, out_ptr):
+        _nv.check(self.lib.tv_cp_dual_vtv(self.geo.ref, _nv.ptr(self.x_bar), _nv.ptr(self.xh_prev), _nv.ptr(self.xh_next), _nv.ptr(self.q),
+                                          sigma, self.reg, out_ptr, _nv.ptr(self.ws), self.stream))
+
+    _GAP_DOC = """For P(x) = 1/2 |x - x0|^2 + reg sum_s |D x|_{F,s} and any dual variable q with |q_s|_F <= reg per spatial site,
+        Dual(q) = <D^T q, x0> - 1/2 |D^T q|^2 <= P(x*) <= P(x), and by strong convexity 1/2 |x - x*|^2 <= P(x) - Dual(q).  The kernel
+        (tv_dual_gap_vtv) sums the gap as 1/2 (x - x0 + D^T q)^2 per voxel + (reg |D x|_{F,s} - <q, D x>_s) per spatial site, both parts
+        >= 0 (Cauchy-Schwarz over the joint vector), and writes nothing but three scalars.
+        fp32 FLOOR: the cancellation inside the second part leaves an absolute error of order eps_fp32 * P, so relative gaps below about
+        1e-6 are not resolvable in fp32; the gap may then come out slightly negative (it is not clamped) and ``run_until`` ends on its
+        iteration limit with ``converged=False``."""
+
+    def _gap_kernel(self, x, q, qscale, b, out):
+        _nv.check(self.lib.tv_dual_gap_vtv(self.geo.ref, _nv.ptr(x), _nv.ptr(b["xp"]), _nv.ptr(b["xn"]), _nv.ptr(q), _nv.ptr(b["qp"]),
+                                           _nv.ptr(b["qn"]), _nv.ptr(self.x0), self.reg, out.data_ptr(), _nv.ptr(self.ws), self.stream))
+
+    duality_gap = _redoc(_GapStopping.duality_gap, """(primal, dual, gap) of the current iterate and dual variable (x, q) as Python floats, between ``run`` / ``run_steps`` / ``step``
+        calls; the state of the loop is not touched.  primal = 1/2 |x - x0|^2 + reg * sum_s |D x|_{F,s}.  Sharded: collective, every rank
         calls it and gets the same numbers.
         """, _GAP_DOC)
     run_until = _redoc(_GapStopping.run_until, tail=_GAP_DOC)

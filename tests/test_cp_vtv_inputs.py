@@ -28,6 +28,10 @@ MIN_SHARE = 0.02
 # register form of hybrid | M = 8 and 9: the last register form of the other schemes and the first generic one
 SHAPES = [(3, 2, 16, 20), (2, 3, 9, 13), (1, 5, 8, 64), (2, 16, 6, 8), (1, 1, 32, 40), (1, 4, 8, 12), (1, 8, 6, 8), (2, 9, 5, 8)]
 WEIGHTINGS = ("plain", "mask", "time_factor", "weight_vol", "no_time")
+# the volumes that tests/test_gpu_cp_vtv.py cuts into z-ranges (register form, generic form) and the weightings it cuts them under: a
+# per-pixel mask that every range shares, and a per-voxel time weight that the ranges cut by planes
+Z_SHAPES = [(5, 2, 16, 20), (5, 9, 6, 8)]
+Z_WEIGHTINGS = ("plain", "weight_vol", "mask")
 
 
 def case_kw(name, shape):
@@ -148,6 +152,24 @@ def test_every_class_of_sites_is_populated(shape, scheme):
                 assert coupled >= MIN_SHARE, (weighting, coupled)
             else:
                 assert coupled == 0.0                                   # one frame: its own norm IS the site's
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+@pytest.mark.parametrize("shape", Z_SHAPES)
+def test_every_class_of_sites_is_populated_in_every_plane_of_the_z_range_volumes(shape, scheme):
+    """``Z_SHAPES`` are not in ``SHAPES``: the same three shares for the (shape, weighting) pairs of the z-range tests, over the volume AND in
+    each of its 5 planes -- a range of one plane must not be all-inside (nothing projected) or all-outside"""
+    for weighting in Z_WEIGHTINGS:
+        for dtype in (np.float64, np.float32):
+            x, q, _, kw = kernel_inputs(shape, scheme, dtype, weighting)
+            _, _, v, _ = ref_dual(x, q, SIGMA, LAM, scheme, kw)
+            what = (shape, scheme, weighting, np.dtype(dtype).name)
+            inside, outside, coupled, _ = shares(v, LAM)
+            assert min(inside, outside, coupled) >= MIN_SHARE, (what, inside, outside, coupled)
+            for z in range(shape[0]):
+                inside, outside, coupled, _ = shares(v[z:z + 1], LAM)
+                print("%s %s %s %s plane %d: inside %.3f outside %.3f coupled %.3f" % (what + (z, inside, outside, coupled)))
+                assert min(inside, outside, coupled) >= MIN_SHARE, (what, z, inside, outside, coupled)
 
 
 def test_joint_projection_is_feasible_and_differs_from_the_per_frame_one():

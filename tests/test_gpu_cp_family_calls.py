@@ -3,8 +3,8 @@ plain Python proxy that forwards every call and notes the entry point's name and
 stopping quantity (``duality_gap()`` or ``residuals()``) must produce a literal sequence of entry points, with tau / sigma / theta EQUAL (as
 doubles, no tolerance) to what ``accel_schedule`` / ``cp_linear_steps`` / ``cp_step_pair`` give for that iteration on the host.
 
-Six classes, ``AcceleratedChambollePock`` and ``HuberChambollePock`` on both of their paths: eight configurations, fp32, schemes upwind and
-hybrid, shape (3, 2, 8, 64) -- the smallest that tv_cp_fused_supported accepts (Nx = 64, whole 16-byte lanes), with an interior plane, more
+Eight classes, ``AcceleratedChambollePock``, ``HuberChambollePock`` and ``AdaptiveHuberChambollePock`` on both of their paths: eleven
+configurations, fp32, schemes upwind and hybrid, shape (3, 2, 8, 64) -- the smallest that tv_cp_fused_supported accepts (Nx = 64, whole 16-byte lanes), with an interior plane, more
 than one frame, unsharded.  A statement about behaviour: nothing here knows how the solvers are written."""
 import numpy as np
 import pytest
@@ -18,7 +18,8 @@ REG, ALPHA, N_STEPS = 5.0, 2.0, 3
 QUERIES = ("tv_cp_fused_supported", "tv_version", "tv_get_option", "tv_cp_zchunk")
 
 # index of (tau, sigma, theta) in the argument list of each entry point that takes one (include/pytv4d.h; argument 0 is the geometry)
-SCALARS = {"tv_cp_dual": dict(sigma=5), "tv_cp_dual_huber": dict(sigma=5), "tv_cp_dual_wtv": dict(sigma=6),
+SCALARS = {"tv_cp_dual": dict(sigma=5), "tv_cp_dual_huber": dict(sigma=5), "tv_cp_dual_wtv": dict(sigma=6), "tv_cp_dual_vtv": dict(sigma=5),
+           "tv_cp_dual_hwtv": dict(sigma=6), "tv_cp_hwtv_sweep": dict(sigma=10, tau=13, theta=14),
            "tv_cp_primal_accel": dict(tau=7, theta=8), "tv_cp_primal_prox": dict(tau=9, theta=10), "tv_cp_primal_kl": dict(tau=7, theta=8),
            "tv_cp_primal_wls": dict(tau=10, theta=11), "tv_cp_accel_sweep": dict(sigma=9, tau=11, theta=12),
            "tv_cp_huber_sweep": dict(sigma=9, tau=12, theta=13), "tv_cp_accel_fixup": dict(tau=7, theta=8)}
@@ -49,6 +50,17 @@ def _linear_steps(S, L2):
     return [S.cp_linear_steps(L2, 1.0, ALPHA / REG)[:3]] * N_STEPS
 
 
+G_MAX = 1.5                 # the largest of the weights ``_weights`` gives: not 1, so steps computed without it differ
+
+
+def _weights(x0):
+    return 0.5 + (x0 > 50).to(x0.dtype)
+
+
+def _adaptive_linear_steps(S, L2):
+    return [S.cp_linear_steps(L2, 1.0, ALPHA / (REG * G_MAX))[:3]] * N_STEPS
+
+
 def _fixed_steps(S, L2):
     return [S.cp_step_pair(L2) + (1.0,)] * N_STEPS
 
@@ -64,8 +76,14 @@ CONFIGS = {
                    "duality_gap", _linear_steps),
     "huber_fused": ("HuberChambollePock", lambda x0: dict(alpha=ALPHA), True, ["tv_cp_huber_sweep", "tv_cp_accel_fixup"], ["tv_dual_gap_huber"],
                     "duality_gap", _linear_steps),
-    "adaptive": ("AdaptiveTVChambollePock", lambda x0: dict(reg_weights=0.5 + (x0 > 50).to(x0.dtype)), None,
+    "adaptive": ("AdaptiveTVChambollePock", lambda x0: dict(reg_weights=_weights(x0)), None,
                  ["tv_cp_dual_wtv", "tv_cp_primal_accel"], ["tv_dual_gap_wtv"], "duality_gap", _accel_steps),
+    "vectorial": ("VectorialTVChambollePock", lambda x0: {}, None, ["tv_cp_dual_vtv", "tv_cp_primal_accel"], ["tv_dual_gap_vtv"], "duality_gap",
+                  _accel_steps),
+    "adaptive_huber_pair": ("AdaptiveHuberChambollePock", lambda x0: dict(reg_weights=_weights(x0), alpha=ALPHA), False,
+                            ["tv_cp_dual_hwtv", "tv_cp_primal_accel"], ["tv_dual_gap_hwtv"], "duality_gap", _adaptive_linear_steps),
+    "adaptive_huber_fused": ("AdaptiveHuberChambollePock", lambda x0: dict(reg_weights=_weights(x0), alpha=ALPHA), True,
+                             ["tv_cp_hwtv_sweep", "tv_cp_accel_fixup"], ["tv_dual_gap_hwtv"], "duality_gap", _adaptive_linear_steps),
     "robust": ("RobustChambollePock", lambda x0: dict(fidelity="l1"), None, ["tv_cp_dual", "tv_cp_primal_prox"],
                ["tv_cp_dual_residual", "tv_cp_primal_prox"], "residuals", _fixed_steps),
     "poisson": ("PoissonChambollePock", lambda x0: {}, None, ["tv_cp_dual", "tv_cp_primal_kl"], ["tv_cp_dual_residual", "tv_cp_primal_kl"],
@@ -115,6 +133,7 @@ def test_calls_and_step_scalars(config, scheme, x0):
 
     if fused:
         # x_bar and its partner change roles with every sweep: (A -> B), (B -> A), (A -> B); the fix-up completes what the sweep wrote
+        # (xbar_in / xbar_out are arguments 1 / 8 of tv_cp_accel_sweep, tv_cp_huber_sweep and tv_cp_hwtv_sweep alike, xbar_out is 5 of the fix-up)
         sweeps, fixups = calls[0:2 * N_STEPS:2], calls[1:2 * N_STEPS:2]
         a, b = sweeps[0][1][1], sweeps[0][1][8]
         assert a == x_bar_before and b is not None and b != a
@@ -131,6 +150,18 @@ def test_adaptive_tv_refuses_the_one_sweep_path(x0):
     with pytest.raises(ValueError) as exc:
         solver.set_fused(True)
     assert str(exc.value) == "set_fused(True): AdaptiveTVChambollePock has no one-sweep path (the one-sweep kernels take a scalar lambda)"
+    solver.set_fused(None)
+    solver.set_fused(False)
+    assert solver.fused is False
+
+
+def test_vectorial_tv_refuses_the_one_sweep_path(x0):
+    import pytv.solvers as S
+    solver = S.VectorialTVChambollePock(x0.clone(), REG, **KW)
+    with pytest.raises(ValueError) as exc:
+        solver.set_fused(True)
+    assert str(exc.value) == ("set_fused(True): VectorialTVChambollePock has no one-sweep path (the one-sweep kernels project each frame's dual "
+                              "vector on its own)")
     solver.set_fused(None)
     solver.set_fused(False)
     assert solver.fused is False

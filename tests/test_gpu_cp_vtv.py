@@ -15,7 +15,8 @@ import torch
 
 from conftest import SCHEMES
 from oracle import tv_oracle as orc
-from test_cp_vtv_inputs import (LAM, SHAPES, SIGMA, WEIGHTINGS, kernel_inputs, np_vectorial, ref_dual, ref_gap, ref_gap_parts, shares, site_norm)
+from test_cp_vtv_inputs import (LAM, SHAPES, SIGMA, WEIGHTINGS, Z_SHAPES, Z_WEIGHTINGS, kernel_inputs, np_vectorial, ref_dual, ref_gap,
+                                ref_gap_parts, shares, site_norm)
 from test_gpu_cp_wtv import (DTYPES, RTOL, WS_FILL, _bits, _explicit_pitch, _geometry, _pads_are_zero, _storage, _uploaders, _untouched,
                              _ws_beyond_the_partials_untouched, _z_channels, noisy_square)
 from test_gpu_cp_wtv import gpu_dual as gpu_dual_per_frame      # tv_cp_dual_wtv (g an array) / tv_cp_dual (g None)
@@ -162,38 +163,51 @@ def test_result_differs_from_the_per_frame_projection_where_it_must(shape, schem
 # ------------------------------------------------------------------------------------------------
 # 4. z-ranges: planes [a, b) with hand-passed halo planes against the whole-volume call
 # ------------------------------------------------------------------------------------------------
-Z_SHAPES = [(5, 2, 16, 20), (5, 9, 6, 8)]                      # register form, generic form
+# Z_SHAPES (tests/test_cp_vtv_inputs.py, where every plane of them is shown to hold all three classes of sites): register form, generic form
+Z_RANGES = ((0, 2), (2, 5), (1, 4), (0, 1), (2, 3), (4, 5))    # (2, 3): one plane with both halo planes at once, what a one-plane rank gets
+Z_CUTS = ((0, 2, 5), (0, 1, 4, 5), (0, 1, 2, 3, 4, 5))         # partitions of [0, 5) into z-ranges; the last: every range is one plane
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("scheme", SCHEMES)
 @pytest.mark.parametrize("shape", Z_SHAPES)
-def test_dual_z_ranges_equal_the_whole_volume(shape, scheme, dtype):
-    x, q, _, kw = kernel_inputs(shape, scheme, dtype, "plain")
-    wq, wvtv = gpu_dual(x, q, SIGMA, LAM, scheme, dtype, kw)
-    parts = {}
-    for a, b in ((0, 2), (2, 5), (1, 4)):
-        keep = {}
-        gq, vtv = gpu_dual(x, q, SIGMA, LAM, scheme, dtype, kw, z_range=(a, b), keep=keep)
-        np.testing.assert_array_equal(_bits(gq), _bits(wq[a:b]), err_msg="planes [%d, %d)" % (a, b))
-        _untouched(keep, ("x", "xp", "xn"))
-        parts[(a, b)] = vtv
-    print("%s %s: parts %.17g + %.17g whole %.17g" % (scheme, np.dtype(dtype).name, parts[(0, 2)], parts[(2, 5)], wvtv))
-    assert abs(parts[(0, 2)] + parts[(2, 5)] - wvtv) <= 1e-12 * wvtv
+def test_dual_z_ranges_equal_the_whole_volume(shape, scheme, dtype, tvopt):
+    """every weighting of ``Z_WEIGHTINGS`` (the per-voxel time weight is cut by planes with the range), the default form and the generic form
+    forced: q of a range is bit for bit the planes of the whole-volume call, inputs and halo planes are untouched, and the scalars of the
+    ranges of a partition of [0, 5) -- (0, 2) + (2, 5), (0, 1) + (1, 4) + (4, 5) -- add up to the whole's"""
+    for weighting in Z_WEIGHTINGS:
+        x, q, _, kw = kernel_inputs(shape, scheme, dtype, weighting)
+        for form in (0, 2):
+            tvopt("TV_VTV_FORM", form)
+            what = "%s %s %s form %d" % (weighting, scheme, np.dtype(dtype).name, form)
+            wq, wvtv = gpu_dual(x, q, SIGMA, LAM, scheme, dtype, kw)
+            parts = {}
+            for a, b in Z_RANGES:
+                keep = {}
+                gq, vtv = gpu_dual(x, q, SIGMA, LAM, scheme, dtype, kw, z_range=(a, b), keep=keep)
+                np.testing.assert_array_equal(_bits(gq), _bits(wq[a:b]), err_msg="%s planes [%d, %d)" % (what, a, b))
+                _untouched(keep, ("x", "xp", "xn"))
+                parts[(a, b)] = vtv
+            print("%s: parts %.17g + %.17g whole %.17g" % (what, parts[(0, 2)], parts[(2, 5)], wvtv))
+            assert abs(parts[(0, 2)] + parts[(2, 5)] - wvtv) <= 1e-12 * wvtv, what
+            assert abs(parts[(0, 1)] + parts[(1, 4)] + parts[(4, 5)] - wvtv) <= 1e-12 * wvtv, what
 
 
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_dual_missing_halo_plane_is_refused_and_nothing_is_written(scheme):
-    x, q, _, kw = kernel_inputs(Z_SHAPES[0], scheme, np.float32, "plain")
+    """both forms (``Z_SHAPES``), a range of three planes and a range of one"""
     # a forward difference reads the next slab, a backward one the previous (central, hybrid: both)
     sides = {"upwind": ("next",), "downwind": ("prev",)}.get(scheme, ("prev", "next"))
-    for side in sides:
-        keep = {}
-        with pytest.raises(ValueError, match=r"x_%s.*halo.*code -2" % side):
-            gpu_dual(x, q, SIGMA, LAM, scheme, np.float32, kw, z_range=(1, 4), keep=keep, drop_halo=side)
-        torch.cuda.synchronize()
-        _untouched(keep, ("x", "q", "xp", "xn"))
-        assert bool((keep["ws"] == WS_FILL).all())
+    for shape in Z_SHAPES:
+        x, q, _, kw = kernel_inputs(shape, scheme, np.float32, "plain")
+        for z_range in ((1, 4), (2, 3)):
+            for side in sides:
+                keep = {}
+                with pytest.raises(ValueError, match=r"x_%s.*halo.*code -2" % side):
+                    gpu_dual(x, q, SIGMA, LAM, scheme, np.float32, kw, z_range=z_range, keep=keep, drop_halo=side)
+                torch.cuda.synchronize()
+                _untouched(keep, ("x", "q", "xp", "xn"))
+                assert bool((keep["ws"] == WS_FILL).all())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -239,21 +253,24 @@ def test_gap_matches_the_reference_and_writes_nothing(shape, scheme, dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_gap_z_range_partials_add_up(scheme, dtype):
-    shape = Z_SHAPES[0]
-    x, _, x0, kw = kernel_inputs(shape, scheme, dtype, "plain")
-    q = feasible_q(shape, scheme, dtype, "plain")
-    ref = ref_gap(x, q, x0, LAM, scheme, kw)
-    whole = gpu_gap(x, q, x0, LAM, scheme, dtype, kw)
-    _check_gap(whole, ref, dtype, "whole")
-    for cut in ((0, 2, 5), (0, 1, 4, 5)):
-        parts = np.zeros(3)
-        for a, b in zip(cut[:-1], cut[1:]):
-            keep = {}
-            parts += np.array(gpu_gap(x, q, x0, LAM, scheme, dtype, kw, z_range=(a, b), keep=keep))
-            _untouched(keep, GAP_INPUTS)
-        print("%s %s cut %r: parts %r whole %r" % (scheme, np.dtype(dtype).name, cut, tuple(parts), whole))
-        for k, scale in enumerate((ref[0], ref[1], ref[3])):
-            assert abs(parts[k] - whole[k]) <= 1e-12 * scale, (cut, k)
+    """M = 2 and the generic count M = 9 (the frame loop over q_prev / q_next), plain and under a per-voxel time weight cut by planes with
+    the range; ``Z_CUTS``: the last cut hands every call one plane, the inner ones with both halo planes of x and of q at once"""
+    for shape in Z_SHAPES:
+        for weighting in ("plain", "weight_vol"):
+            x, _, x0, kw = kernel_inputs(shape, scheme, dtype, weighting)
+            q = feasible_q(shape, scheme, dtype, weighting)
+            ref = ref_gap(x, q, x0, LAM, scheme, kw)
+            whole = gpu_gap(x, q, x0, LAM, scheme, dtype, kw)
+            _check_gap(whole, ref, dtype, "%s %s whole" % (shape, weighting))
+            for cut in Z_CUTS:
+                parts = np.zeros(3)
+                for a, b in zip(cut[:-1], cut[1:]):
+                    keep = {}
+                    parts += np.array(gpu_gap(x, q, x0, LAM, scheme, dtype, kw, z_range=(a, b), keep=keep))
+                    _untouched(keep, GAP_INPUTS)
+                print("%s %s %s %s cut %r: parts %r whole %r" % (shape, weighting, scheme, np.dtype(dtype).name, cut, tuple(parts), whole))
+                for k, scale in enumerate((ref[0], ref[1], ref[3])):
+                    assert abs(parts[k] - whole[k]) <= 1e-12 * scale, (shape, weighting, cut, k)
 
 
 # ------------------------------------------------------------------------------------------------

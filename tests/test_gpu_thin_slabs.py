@@ -6,7 +6,9 @@ one plane, partitions with a remainder, ranks that sit exactly on an overlap thr
 that disagree about the chunks of the one-sweep kernel.
 
 Expected values are fp64 runs on the UNSHARDED volume: ``orc.chambolle_pock`` / ``orc.admm`` / ``orc.subgradient_descent``, and for the
-extrapolated Chambolle-Pock solvers the NumPy restatements of their own test files (imported, not copied).  Each rank's result is compared
+eight extrapolated Chambolle-Pock solvers (``AcceleratedChambollePock``, ``HuberChambollePock``, ``AdaptiveTVChambollePock``,
+``AdaptiveHuberChambollePock``, ``VectorialTVChambollePock``, ``RobustChambollePock``, ``PoissonChambollePock``, ``WeightedChambollePock``:
+twelve solver classes in all) the NumPy restatements of their own test files (imported, not copied).  Each rank's result is compared
 with ``slab.local`` of it, the loss history and the certificate (``duality_gap()`` / ``residuals()``) with the global value.
 
 Tolerances are those the project states already:
@@ -111,6 +113,8 @@ def _worker(rank, world, port, nzg, dtype_name, jobs, ret):
             elif job.get("cert") == "res":
                 res["cert"] = dict(s.residuals())
                 res["r0"] = s.initial_residual()
+            if hasattr(s, "g_max"):
+                res["g_max"] = s.g_max            # AdaptiveHuberChambollePock: the maximum of g its steps were computed from
             if job.get("until") is not None:
                 t = build()
                 loss, info = t.run_until(*job["until"])
@@ -167,6 +171,9 @@ def _plan(shape, dtype_name, sizes):
     import test_gpu_cp_prox as t_prox
     import test_gpu_cp_wls as t_wls
     import test_gpu_cp_wtv as t_wtv
+    import test_cp_vtv_inputs as t_vin
+    import test_gpu_cp_hwtv_sweep as t_hwtv        # (the restatement and certificate that tests/test_gpu_cp_hwtv.py imports from there)
+    import test_gpu_cp_vtv as t_vtv
     from test_gpu_dual_gap import ref_gap
     f32 = dtype_name == "float32"
     sweep_ok = shape[3] >= 64 and shape[3] % (4 if f32 else 2) == 0      # tv_cp_fused_supported: whole 16-byte lanes, Nx >= 64, either precision
@@ -209,7 +216,7 @@ def _plan(shape, dtype_name, sizes):
                 add("cpw_%s_%s" % (way, scheme), "ChambollePock", x0, (7.0,), dict(KW, scheme=scheme, mask_static=W, **how), N_IT,
                     dict(x=vx, loss=vloss, kind="cp"))
 
-    # ---- a. the six extrapolated solvers (kernel pair on a slab)
+    # ---- a. the eight extrapolated solvers (kernel pair on a slab)
     for scheme in TWO:
         # AcceleratedChambollePock
         d = _f32(t_acc.square_plus_noise(shape))
@@ -240,6 +247,24 @@ def _plan(shape, dtype_name, sizes):
         add("wtv_%s" % scheme, "AdaptiveTVChambollePock", d, (t_wtv.REG, g), dict(XKW, scheme=scheme), N_IT,
             dict(x=wx, loss=wloss, kind="xcp", cert=(fid + t_wtv.REG * wtv, gap), scale=float(np.max(np.abs(d)))), cert="gap",
             until=(1e-3, 4, 2), until_want=None)
+        # AdaptiveHuberChambollePock: the same data and weight map; its steps come from the maximum of g over ALL ranks
+        wx, wloss, wq = t_hwtv.np_hwtv_cp(d, g, N_IT, t_hub.REG, 2.0, scheme, XKW)
+        hub, fid, gap, _ = t_hwtv.np_gap_hwtv(wx, wq, d, g, t_hub.REG, 2.0, scheme, XKW)
+        add("hwtv_%s" % scheme, "AdaptiveHuberChambollePock", d, (t_hub.REG, g, 2.0), dict(XKW, scheme=scheme), N_IT,
+            dict(x=wx, loss=wloss, kind="xcp", cert=(fid + t_hub.REG * hub, gap), scale=float(np.max(np.abs(d))), g_max=float(g.max())),
+            cert="gap", one_sweep_refused=refusal, until=(1e-3, 4, 2), until_want=None)
+        # VectorialTVChambollePock: it has no one-sweep path on any geometry, and says so before it looks at the slab
+        d = _f32(t_vtv.coupled_square(shape))
+        states, state, wloss = [], None, []
+        for n in (2, 2, 2):
+            wx, part, state = t_vin.np_vectorial(d, n, t_vtv.REG, scheme, XKW, state=state)
+            wloss.append(part)
+            vtv, fid, gap, _ = t_vin.ref_gap(state[0], state[2], d, t_vtv.REG, scheme, XKW)
+            states.append((fid + t_vtv.REG * vtv, gap))
+        rel = float(np.sqrt((states[0][1] / states[0][0]) * (states[1][1] / states[1][0])))
+        add("vtv_%s" % scheme, "VectorialTVChambollePock", d, (t_vtv.REG,), dict(XKW, scheme=scheme), N_IT,
+            dict(x=wx, loss=np.concatenate(wloss), kind="xcp", cert=states[2], scale=float(np.max(np.abs(d)))), cert="gap",
+            one_sweep_refused="VectorialTVChambollePock has no one-sweep path", until=(rel, 6, 2), until_want=_gap_count(states, rel, 2, 6))
         # RobustChambollePock("l1")
         d = np.asarray(t_prox.square_with_impulses(shape))
         tau = t_prox.TAU_S
@@ -341,6 +366,8 @@ def test_sharded_solvers_on_thin_slabs_equal_the_unsharded_oracle(nzg, world, fr
             # ---- the certificate: the same numbers on every rank, and the oracle's
             if "cert" in got:
                 assert got["cert"] == got0["cert"], msg
+            if "g_max" in chk:
+                assert got["g_max"] == chk["g_max"], msg          # the maximum over ALL ranks, on every rank
             if "until" in got:
                 assert got["until"] == got0["until"] and got["until"][0] == got["until"][2], msg      # every rank stops at the same iteration
                 if chk.get("until_want") is not None:
